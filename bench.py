@@ -3,6 +3,7 @@
 bench.py — headline benchmark of the MI355X Jubjub engine (BASELINE.json metric: Jubjub scalar-muls/sec).
 
   python bench.py --gpus N --steps K --warmup W [--workload varbase|fixedbase|msm|decompress] [--log2n L] [--scaling weak|strong]
+                  [--dump-outputs DIR]
 
 One "step" = PASSES back-to-back passes of the hot path over one batch of synthetic inputs already resident in HBM (the
 pass count per workload is fixed below and reported in `config`, it only makes the timed region long enough for the
@@ -45,6 +46,7 @@ The JSON carries:
                encodings for the decoder) recomputed by the oracle from the unit indices: true / false.
   cpu_baseline the oracle's C port of the reference algorithm (exact 252-step ladder, 4x64 Montgomery limbs) timed on this
                box's host cores on a bounded sample: one thread and all cores, CPU model stated (N = 1 only).
+  dump_outputs with --dump-outputs DIR: the .npy files written from the last timed step's output and how their rows were sampled.
 """
 import argparse
 import hashlib
@@ -57,7 +59,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before the first HIP call of this process: see jubjub_amd/_lib.py
 
 HBM_PEAK_GBPS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 NOMINAL_PEAK_IMAD32 = 1024 * 16 * 2.4e9   # 1024 SIMDs x 16 lanes x 2.4 GHz boost clock: one 32x32+64 multiply-add per lane per 4-cycle wave64 issue
@@ -108,6 +109,9 @@ DEFAULT_LOG2N = {"varbase": 20, "fixedbase": 24, "msm": 20, "decompress": 23}
 UNIT = {"varbase": "scalar-muls/s", "fixedbase": "scalar-muls/s", "msm": "terms/s", "decompress": "points/s"}
 GEN_U = 0x62EDCBB8BF3787C88B0F03DDD60A8187CAF55D1B29BF81AFE4B3D35DF1A7ADFE   # generator (u, 11), reference src/lib.rs:1380-1396
 SAMPLE_STRIDE = 1 << 10
+# --dump-outputs: an output of more rows than this keeps a fixed sample of DUMP_ROWS of them, drawn with DUMP_SEED (16 MB of float32 at 64 bytes per row)
+DUMP_ROWS = 1 << 16
+DUMP_SEED = 0x44554D50
 BLOCK_LOG2 = 14          # besides the strided sample: one CONTIGUOUS block of 2^14 units (whole waves, whole workgroups) recomputed by the oracle
 # edge encodings injected into the decoder's input at fixed global indices: (index, kind)
 INJECT_FIRST, INJECT_STEP = 1000, 4096
@@ -125,6 +129,33 @@ def host_bytes(x):
     import numpy as np
 
     return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: the arrays of one step's output (a tensor / array of result bytes, or the decoder's (points, ok) pair) as
+    d/out.npy (and d/ok.npy), float32 with one element per byte, rows in unit order; above DUMP_ROWS rows the same seeded sample of
+    rows for every run of the same batch size.  Returns what the JSON line records about it."""
+    import numpy as np
+
+    arrays = dict(zip(("out", "ok"), out if isinstance(out, tuple) else (out,)))
+    n = arrays["out"].shape[0] if arrays["out"].ndim > 1 else 1           # the MSM returns one 64-byte point
+    rows = None
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    os.makedirs(d, exist_ok=True)
+    files = {}
+    for name, x in arrays.items():
+        if rows is not None and hasattr(x, "cpu"):
+            import torch
+
+            x = x[torch.from_numpy(rows).to(x.device)]                   # gathered on the device: only the sample crosses to the host
+        elif rows is not None:
+            x = np.asarray(x)[rows]
+        h = host_bytes(x).astype(np.float32)
+        np.save(os.path.join(d, name + ".npy"), h)
+        files[name + ".npy"] = list(h.shape)
+    return {"dir": d, "files": files, "rows_of": n,
+            "sample": None if rows is None else "%d rows drawn without replacement by numpy default_rng(%#x).choice(%d, %d), sorted" % (DUMP_ROWS, DUMP_SEED, n, DUMP_ROWS)}
 
 
 def parse():
@@ -160,7 +191,13 @@ def parse():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="jj_ctx_set_option for every context of the run (repeatable), e.g. --opt msm_lanes=1 --opt msm_front1=0; "
                     "host_tail_scalar=1 is process-wide.  The library reads no JJ_* environment variable.")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target wall time of each CPU baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0: write what the last timed step returned as DIR/<name>.npy, float32, one element per result byte (out.npy; the decoder "
+                         "also ok.npy); an output of more than %d rows keeps the same seeded sample of %d rows in every run" % (DUMP_ROWS, DUMP_ROWS))
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ self-launch
@@ -699,6 +736,8 @@ def run(a):
         # each rank's own time per step before the closing barrier (ms_per_step is the max over ranks, barrier included): stragglers show here
         "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
     }
+    if a.dump_outputs and rank == 0:
+        res["dump_outputs"] = dump_outputs(a.dump_outputs, out)          # the last timed step's output (host modes: as copied back above)
     if host:
         res["pcie_inclusive"] = True
         res["config"]["host_buffers"] = {"pinned": "page-locked (jj_host_alloc), reused by every pass",

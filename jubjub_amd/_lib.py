@@ -4,10 +4,9 @@ import ctypes as C
 import os
 
 # HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  A context with jobs in flight uses up to six streams (launch, two
-# copy streams, three MSM lanes since round 6): with four queues two of them share one and the pipelines run 1.7-2x slower (profiles/r4_pcie_inclusive.txt).  The C
-# library never touches the environment (it warns once on stderr when it creates its fifth stream with fewer than 8 queues configured); this
-# PYTHON package sets the variable, if the application has not, before the HIP runtime is loaded -- a HIP runtime variable, not a switch of ours.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# copy streams, three MSM lanes since round 6): with four queues two of them share one and the pipelines run 1.7-2x slower (profiles/r4_pcie_inclusive.txt).  The queue
+# count is the application's and its environment's to choose, a HIP runtime variable, not a switch of ours: neither this package nor the C library
+# touches the environment (the library warns once on stderr when it creates its fifth stream with fewer than 8 queues configured).
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JJ_LIB_PATH") or os.path.join(HERE, "lib", "libjubjub_hip.so")   # JJ_LIB_PATH: A/B builds of the same library

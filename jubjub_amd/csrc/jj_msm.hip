@@ -234,7 +234,7 @@ static int msm_lane(jj_ctx* c, int k, MsmLane** out) {
     if (k >= 2) {
       static std::atomic<bool> warned{false};
       const char* q = getenv("GPU_MAX_HW_QUEUES");
-      if ((!q || atoi(q) < 8) && !warned.exchange(true)) fprintf(stderr, "libjubjub_hip: MSM jobs in flight use 5+ streams; export GPU_MAX_HW_QUEUES=8 before the first HIP call (or set option msm_lanes=1), streams sharing a hardware queue serialise\n");
+      if ((!q || atoi(q) < 8) && !warned.exchange(true)) fprintf(stderr, "libjubjub_hip: MSM jobs in flight use 5+ streams and fewer than 8 hardware queues are configured (HIP's GPU_MAX_HW_QUEUES): streams sharing a queue serialise (option msm_lanes=1 keeps the jobs on one stream)\n");
     }
     HIPCHK(c, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
     HIPCHK(c, hipEventCreateWithFlags(&L.ready_ev, hipEventDisableTiming));

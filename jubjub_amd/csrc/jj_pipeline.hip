@@ -275,7 +275,7 @@ int dev_to_host_bounced(jj_ctx* c, void* host, const void* dev, size_t bytes) {
 // buffer pipeline (compute, copy in, copy out) and one more per extra MSM lane; beside PyTorch's or the caller's own streams that
 // exceeds four, and two streams that share a hardware queue serialise -- measured: jj_multi_* with a second context in the process
 // 268 -> 523 M fixed-base scalar-muls/s, a fourth pipeline stream 316 -> 520 M/s (profiles/r4_pcie_inclusive.txt).  The runtime reads
-// the variable when it initialises (first HIP call).  It is the APPLICATION's to set (bench.py does): rounds 3-4 set it
+// the variable when it initialises (first HIP call).  It is the APPLICATION's to set: rounds 3-4 set it
 // from a load-time constructor here, which changed the HIP configuration of the whole host process behind its back.
 
 // ---------------------------------------------------------------------------------------------------- host buffers

@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/box_sample.sh r6 2'     then locally: cp gpurun_out/r6_bench_*_box2.json profiles/ ; python tools/box_samples.py r6
 TAG=${1:-r6}; K=${2:-2}
 cd "$(dirname "$0")/.."
-export TMPDIR=/tmp GPU_MAX_HW_QUEUES=8
+export TMPDIR=/tmp
 mkdir -p gpurun_out
 python bench.py > gpurun_out/${TAG}_bench_default_box$K.json 2>/dev/null
 python bench.py --workload fixedbase --no-cpu-baseline > gpurun_out/${TAG}_bench_fixedbase_box$K.json 2>/dev/null

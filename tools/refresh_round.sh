@@ -5,7 +5,6 @@ set -e
 TAG=${1:-r6}
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=8        # the host-buffer pipeline beside torch's streams (include/jubjub_hip.h: the application sets it, not the library)
 mkdir -p gpurun_out
 python tools/profile_round.py --tag $TAG > gpurun_out/${TAG}_profile.log 2>&1
 python bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
