@@ -154,7 +154,7 @@ def test_varbase_edges(eng, golden):
 
 
 def test_varbase_per_lane_and_per_quad_kernels(golden, monkeypatch):
-    """Batches up to JJ_VB_QUAD_MAX run one scalar multiplication per quad of lanes, larger ones one per lane; both
+    """Batches up to vb_quad_max (option) run one scalar multiplication per quad of lanes, larger ones one per lane; both
     kernels on the same inputs (edge scalars x special points, random, sizes around the wave/quad granularity)."""
     from jubjub_amd import Engine
 
@@ -181,7 +181,7 @@ def test_varbase_per_lane_and_per_quad_kernels(golden, monkeypatch):
 def test_varbase_constant_time_ladder(golden, monkeypatch, window, quad_max):
     """jj_varbase_mul_ct: no scalar-dependent address or branch, the reference's conditional_select discipline (src/lib.rs:334-343,
     357-379).  Signed 3-bit windows (default; table {P, 2P} in registers, {3P, 4P} in a per-lane LDS slot that is read whole for every
-    window, mask selects) and signed 2-bit windows (JJ_VB_CT_WINDOW=2: {P, 2P} in registers alone): every edge scalar on random /
+    window, mask selects) and signed 2-bit windows (option vb_ct_window=2: {P, 2P} in registers alone): every edge scalar on random /
     torsion / generator / identity points, random inputs, ragged and empty batches, digit patterns that put every window value into
     every position class -- the same points as the table ladder and the oracle.  quad_max 32768: the batch runs one scalar
     multiplication per quad of lanes (k_varbase_ct_quad: every lane keeps its own coordinate of {P .. 4P} in registers); 0: one per lane."""
@@ -235,7 +235,7 @@ def test_varbase_shared_scalar(eng, golden):
 
 
 def test_varbase_shared_scalar_kernel_large_ragged_batch(eng, golden, monkeypatch):
-    """above JJ_VB_QUAD_MAX the shared-scalar kernel runs (k_varbase<.., SHARED>: the scalar is read through a wave-uniform
+    """above vb_quad_max (option) the shared-scalar kernel runs (k_varbase<.., SHARED>: the scalar is read through a wave-uniform
     address, its digits live in scalar registers); ragged batch sizes exercise the waves' work cursor"""
     from jubjub_amd import Engine
 
@@ -374,7 +374,7 @@ def test_msm(eng):
 
 @pytest.mark.parametrize("small_max", ["0", "100000"])
 def test_msm_small_batch_path_and_pippenger_on_the_same_inputs(monkeypatch, small_max):
-    """JJ_MSM_SMALL_MAX: the two-launch small-batch path (per-term tables, 64 windows of 3-4 bits; default up to 2^14 terms) and
+    """Option msm_small_max: the two-launch small-batch path (per-term tables, 64 windows of 3-4 bits; default up to 2^14 terms) and
     Pippenger, each forced over every size: ragged sizes around the 128-quad workgroups, edge scalars, identity / torsion points."""
     from jubjub_amd import Engine
 
@@ -449,9 +449,11 @@ def test_msm_around_the_large_input_switch(eng):
 
 
 def test_msm_big_bucket_list_overflow(eng):
-    """128 distinct scalars repeated over 2^17 terms: every non-empty bucket holds 1024 entries = 64 chunk heads, and there are about
-    128 x 23 of them -- more than the big-bucket work list holds (2048), so the fix-up's pairs of lanes also run their serial
-    fallback, next to a full work list for the workgroup-per-bucket kernel."""
+    """128 distinct scalars repeated over 2^17 terms: every non-empty bucket holds 1024 entries, i.e. more chunk heads than the
+    FIXUP_SERIAL_MAX (32) a pair of lanes of k_msm_fixup walks itself, and there are about 128 x 23 such buckets.  The chunked path
+    folds every one of them inside k_msm_fixup: the whole wave takes a big bucket after the pairs' own buckets (64 lanes over the heads,
+    a butterfly over the lanes).  There is no work list and no k_msm_fixup_big launch on this path any more (only the segment path's
+    merge list still uses that kernel); the name recalls the work list of earlier rounds."""
     n = 1 << 17
     base = rand_scalars(71, 128, full_width=True)
     S = np.ascontiguousarray(base[np.arange(n) % 128])
@@ -462,9 +464,9 @@ def test_msm_big_bucket_list_overflow(eng):
 @pytest.mark.parametrize("window", [16, 17, 19, 20, 21, 23, 28, 32])
 @pytest.mark.parametrize("sort", ["2pass", "1pass"])
 def test_msm_window_counts_both_sorts(monkeypatch, window, sort):
-    """JJ_MSM_WINDOWS: W windows tiling the 253 scalar bits exactly (16: 13 windows of 16 bits + 3 of 15, the default from 2^20
+    """Option msm_windows: W windows tiling the 253 scalar bits exactly (16: 13 windows of 16 bits + 3 of 15, the default from 2^20
     terms; 21: one of 13 bits + 20 of 12; 23: all 11 bits; ...) forced on small inputs, with the two-pass sort (coarse bin, then
-    the low bits in LDS; always taken above 4096 buckets per window) and the single-pass one (JJ_MSM_SORT decides at exactly 4096):
+    the low bits in LDS; always taken above 4096 buckets per window) and the single-pass one (option msm_sort_two_pass decides at exactly 4096):
     ragged sizes, a bin far larger than the LDS stage (equal scalars), zero digits, the largest top-window digit."""
     from jubjub_amd import Engine
 
@@ -495,7 +497,7 @@ def test_msm_window_counts_both_sorts(monkeypatch, window, sort):
 
 @pytest.mark.parametrize("window,rows,l2chunk", [(16, 8, 0), (16, 4, 8), (16, 32, 2), (16, 0, 0), (17, 4, 0), (17, 16, 4), (19, 8, 0), (20, 2, 16), (23, 4, 0), (32, 2, 0)])
 def test_msm_two_level_bucket_reduce(monkeypatch, window, rows, l2chunk):
-    """JJ_MSM_REDUCE_L1 / JJ_MSM_REDUCE_L2_CHUNK: the two-level bucket reduce (lane-form column sums S_m, T_m over `rows` rows of the
+    """Options msm_reduce_l1 / msm_reduce_l2_chunk: the two-level bucket reduce (lane-form column sums S_m, T_m over `rows` rows of the
     bucket matrix, then the quad chain over the columns; the default from 16 384 buckets per window) forced over window layouts with
     one and two window widths, every level-2 chunk length class, one workgroup and several per window, and switched off (rows = 0);
     ragged sizes, equal scalars (one bucket per window holds everything), zero digits and the largest top-window digit."""
@@ -535,7 +537,7 @@ def test_msm_two_level_bucket_reduce(monkeypatch, window, rows, l2chunk):
 @pytest.mark.parametrize("mode", ["separate", "fused"])
 @pytest.mark.parametrize("window", [16, 17, 18])
 def test_msm_two_pass_sort_histogram_modes(monkeypatch, mode, window):
-    """JJ_MSM_SORT_HIST: the coarse histogram of the two-pass sort taken inside the conversion kernel, the tiles' runs reserved with global atomics
+    """Option msm_sort_hist_fused: the coarse histogram of the two-pass sort taken inside the conversion kernel, the tiles' runs reserved with global atomics
     (k_msm_convert_hist; the default up to 3 x 2^20 terms), against the separate histogram + plan kernels (round 4; the default above): ragged sizes around
     the 1024-term and 4096-term workgroups and the 8192-term tiles, a window partition (slots != windows), equal scalars (one bin holds every entry), zeros."""
     from jubjub_amd import Engine
@@ -579,7 +581,7 @@ def test_msm_back_to_back_sizes(monkeypatch):
 
 
 def test_msm_multipass(monkeypatch):
-    """Inputs larger than one Pippenger pass are folded pass by pass (pass size shrunk here via the env knob)."""
+    """Inputs larger than one Pippenger pass are folded pass by pass (pass size shrunk here with option msm_pass_log2)."""
     from jubjub_amd import Engine
 
     opts = {}
@@ -622,7 +624,7 @@ def test_msm_async_jobs_interleaved(eng):
 
 @pytest.mark.parametrize("lanes", ["1", "3", "4"])
 def test_msm_jobs_over_several_lanes(monkeypatch, lanes):
-    """JJ_MSM_LANES: device-pointer jobs of jj_msm_begin alternate over the context's MSM lanes (own streams and workspaces; default 2),
+    """Option msm_lanes: device-pointer jobs of jj_msm_begin alternate over the context's MSM lanes (own streams and workspaces; default 3),
     so the dependent chains of one MSM overlap the sort / accumulation of the next: mixed sizes (small-batch path, one-pass and
     two-pass Pippenger, multi-pass), more jobs in flight than lanes, workspaces that grow while other lanes are busy, results
     written to device memory, and the synchronous jj_msm in between (lane 0)."""
@@ -694,7 +696,7 @@ def test_msm_partial_records_term_and_window_partition(eng, G):
 def test_msm_gathered_records_folded_on_the_device(monkeypatch, fold):
     """jj_msm_combine_dev (what jj_msm_allgather runs after ncclAllGather): G device-resident records are added window by window on the
     device into ONE record (k_msm_fold_records) before the host tail -- both partitions, G = 2, 3, 8 and 70 (more records than the
-    fold's 64 quads), an empty shard between the others, and records of different window layouts (host fallback).  JJ_MSM_FOLD=host
+    fold's 64 quads), an empty shard between the others, and records of different window layouts (host fallback).  msm_fold_dev=0
     keeps round 4's path (every record copied, the host adds them): both must give the oracle's point."""
     import torch
 
