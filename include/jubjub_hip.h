@@ -296,6 +296,21 @@ int jj_msm_finish(jj_msm_job* job, void* out64);
  * stream (jj_msm does: D2H of the record + host tail + H2D of the point); use jj_msm / jj_msm_begin for latency and throughput.
  * At most 2^24 terms per call; inputs may be host arrays (staged) or device arrays. */
 int jj_msm_dev(jj_ctx*, size_t n, const void* scalars32, const void* points64, void* out64_dev);
+/* B independent MSMs of n terms each: out64[b] = to_affine(sum_i points[b][i] * scalars[b][i]) for b < B; every row equals
+ * jj_msm(ctx, n, row scalars, row points) byte for byte (raw 32-byte scalars, low 252 bits used; exact on the whole curve).
+ * VARIABLE-TIME, like jj_msm: table addresses depend on the scalars' digits.
+ *   scalars32  B x n x 32 bytes, row-major
+ *   points64   n x 64 bytes when points_shared = 1 (every row uses the same points), B x n x 64 bytes when points_shared = 0
+ *   out64      B x 64 bytes
+ * B = 0 succeeds and touches nothing; n = 0 writes the identity (0, 1) to every row (scalars32 and points64 may then be NULL).
+ * JJ_ERR_INVALID: a NULL context, a NULL pointer with a non-zero size, points_shared other than 0 or 1, B * n * 64 beyond size_t.
+ * n <= 8192 (MSM_BATCH_MAX): the whole batch runs in a few launches on the context's stream (per-term tables {0..8}P as in jj_msm's
+ * small-batch layout, one wave per row and slice of its terms, one lane per window, a device-side Horner chain and inversion per
+ * row); with device pointers the call only queues that work and returns, with any host pointer it returns with the results in
+ * host memory.  Tables of distinct points are built for at most 2^18 terms at a time (340 MB of device workspace): larger batches
+ * run in rounds of whole rows.  n > 8192: every row is a jj_msm_begin job (device-pointer rows alternate over the context's
+ * MSM lanes) finished by the host tail, and the call returns only after every row is finished, whatever the pointers. */
+int jj_msm_batch(jj_ctx*, size_t B, size_t n, const void* scalars32, const void* points64, int points_shared, void* out64);
 /* MSM cut across devices or ranks.  jj_msm_partial leaves the RECORD of partial window sums instead of the
  * point: JJ_MSM_PARTIAL_BYTES bytes (64-byte header: magic, version, number of windows W, 1, bit mask of the windows
  * present, n; then one 128-byte point per window: U, V, Z and T = T1 T2, each the 256-bit little-endian integer of
@@ -389,6 +404,9 @@ int jj_multi_fixedbase_table_destroy(jj_multi* m, jj_mtable* t);
 int jj_multi_fixedbase_mul(jj_multi* m, const jj_mtable* t, size_t n, const void* scalars32, void* out64);
 int jj_multi_decompress(jj_multi* m, size_t n, const void* in32, unsigned flags, void* out64, uint8_t* ok);
 int jj_multi_msm(jj_multi* m, size_t n, const void* scalars32, const void* points64, void* out64);
+/* jj_msm_batch over the devices: contiguous blocks of rows, one block per device, no exchange between devices (shared points go
+ * to every device).  HOST pointers, like the other jj_multi_* calls; a device may receive no rows (B smaller than the device count). */
+int jj_multi_msm_batch(jj_multi* m, size_t B, size_t n, const void* scalars32, const void* points64, int points_shared, void* out64);
 /* Last step of an MSM cut across devices or processes (the reference's `Sum`, src/lib.rs:183-193, over the partial sums): adds
  * `count` partial points (canonical affine, 64 bytes each) -> one affine point.  HOST pointers, no context: a short chain of
  * dependent additions and one inversion, run on the calling thread with the arithmetic of the MSM's own host tail.

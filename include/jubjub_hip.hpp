@@ -289,6 +289,37 @@ inline Bytes64 msm(const Context& c, const AffineBatch& points, const FrBatch& s
   return out;
 }
 
+// B independent sums in one call (jj_msm_batch): row b = sum_i points[i] * scalars[b][i], every row over the SAME points ...
+inline AffineBatch msm_batch(const Context& c, const AffineBatch& points, const std::vector<FrBatch>& scalars) {
+  const size_t n = points.len();
+  std::vector<Bytes32> flat;
+  flat.reserve(scalars.size() * n);
+  for (const FrBatch& s : scalars) {
+    if (s.len() != n) throw Error(JJ_ERR_INVALID, "length mismatch");
+    flat.insert(flat.end(), s.to_bytes().begin(), s.to_bytes().end());
+  }
+  std::vector<Bytes64> out(scalars.size());
+  c.check(jj_msm_batch(c.raw(), scalars.size(), n, flat.data(), points.coords().data(), 1, out.data()));
+  return AffineBatch(c, std::move(out));
+}
+// ... or row b = sum_i points[b][i] * scalars[b][i], every row over its own points (all rows of one length)
+inline AffineBatch msm_batch(const Context& c, const std::vector<AffineBatch>& points, const std::vector<FrBatch>& scalars) {
+  if (points.size() != scalars.size()) throw Error(JJ_ERR_INVALID, "one point batch per scalar batch");
+  const size_t n = points.empty() ? 0 : points[0].len();
+  std::vector<Bytes32> fs;
+  std::vector<Bytes64> fp;
+  fs.reserve(scalars.size() * n);
+  fp.reserve(points.size() * n);
+  for (size_t b = 0; b < points.size(); b++) {
+    if (points[b].len() != n || scalars[b].len() != n) throw Error(JJ_ERR_INVALID, "length mismatch");
+    fs.insert(fs.end(), scalars[b].to_bytes().begin(), scalars[b].to_bytes().end());
+    fp.insert(fp.end(), points[b].coords().begin(), points[b].coords().end());
+  }
+  std::vector<Bytes64> out(points.size());
+  c.check(jj_msm_batch(c.raw(), points.size(), n, fs.data(), fp.data(), 0, out.data()));
+  return AffineBatch(c, std::move(out));
+}
+
 // The same sum with the host tail of one MSM overlapping the kernels of the next (jj_msm_begin / jj_msm_finish): the job owns copies
 // of its inputs until it is finished
 struct AllRanks { bool by_windows = false; };      // MsmJob over every rank of the communicator lent with set_comm (jj_msm_allgather_begin)

@@ -54,6 +54,7 @@ _SIGS.update({
     "jj_ctx_set_comm": [_vp, C.c_int, C.c_int, _vp],
     "jj_msm_allgather": [_sz, _vp, _vp, C.c_int, _vp],
     "jj_msm_allgather_begin": [_sz, _vp, _vp, C.c_int, C.POINTER(_vp)],
+    "jj_msm_batch": [_sz, _sz, _vp, _vp, C.c_int, _vp],
     "jj_decompress": [_sz, _vp, C.c_uint, _vp, _u8p],
     "jj_compress": [_sz, _vp, _vp],
     "jj_batch_normalize": [_sz, _vp, _vp],
@@ -78,6 +79,7 @@ _SIGS.update({
     "jj_multi_fixedbase_mul": [_vp, _sz, _vp, _vp],
     "jj_multi_decompress": [_sz, _vp, C.c_uint, _vp, _u8p],
     "jj_multi_msm": [_sz, _vp, _vp, _vp],
+    "jj_multi_msm_batch": [_sz, _sz, _vp, _vp, C.c_int, _vp],
 })
 
 EXPORTS = sorted(list(_SIGS) + ["jj_ctx_create", "jj_ctx_destroy", "jj_last_error", "jj_version", "jj_device_info", "jj_recommended_wnaf_for_num_scalars",

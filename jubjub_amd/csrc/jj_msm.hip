@@ -410,6 +410,104 @@ JJ_API int jj_msm_dev(jj_ctx* c, size_t n, const void* scalars, const void* poin
   hipLaunchKernelGGL(k_msm_finish_dev, dim3(1), dim3(64), 0, c->stream, (const u32*)L->rec.p, out64_dev);
   return finish(c, false);
 }
+// ---- B independent MSMs of n terms each (jj_msm_batch).  Up to MSM_BATCH_MAX terms per row the batched kernels take the whole
+// batch (k_msm_batch_tables / _sum / _finish, jj_msm_kernels.h) on the context's stream; above it every row is an MSM job of its own
+// (msm_begin_locked: device-pointer rows alternate over the context's MSM lanes), finished by the host tail before the call returns.
+// MSM_BATCH_MAX: crossover with the jobs route, profiles/r7_msm_batch.txt.
+constexpr size_t MSM_BATCH_MAX = 1 << 13;
+// workspaces per round: the tables of distinct points cover at most MSM_BATCH_TABLE_TERMS terms (1296 B each: 340 MB), the rows beyond
+// go through in further rounds; the window sums of at most MSM_BATCH_ROWS rows (9 KB each) wait for one finish launch
+constexpr size_t MSM_BATCH_TABLE_TERMS = 1 << 18;
+constexpr size_t MSM_BATCH_ROWS = 1 << 13;
+// a row's terms are cut into slices (one wave each) until rows x slices reaches MSM_BATCH_WAVES waves (two per SIMD of 256 CUs),
+// with at least MSM_BATCH_SLICE_MIN terms per slice
+constexpr size_t MSM_BATCH_WAVES = 2048;
+constexpr size_t MSM_BATCH_SLICE_MIN = 16;
+static size_t msm_batch_slices(size_t rows, size_t n) {
+  const size_t want = (MSM_BATCH_WAVES + rows - 1) / rows, most = std::max<size_t>(1, n / MSM_BATCH_SLICE_MIN);
+  return std::max<size_t>(1, std::min(want, most));
+}
+// rows [0, B) of device arrays -> out (device), all on the context's stream.  Workspaces of lane 0 (ordered with jj_msm by the stream):
+// buf[1] tables, buf[2] window sums, buf[3] slice partials, buf[4] per-row counters
+static int msm_batch_enqueue(jj_ctx* c, size_t B, size_t n, const uint8_t* ds, const uint8_t* dp, bool shared, uint8_t* dout) {
+  MsmLane& L = c->lanes[0];
+  MsmParams mp;
+  msm_layout(mp, SM_W, 0, 1);
+  const size_t TAB = (size_t)SM_SLOTS * ENIELS_WORDS * 4, SUMS = (size_t)SM_W * MSM_BATCH_PT_WORDS * 4;
+  const size_t round_rows = shared ? MSM_BATCH_ROWS : std::max<size_t>(1, std::min(MSM_BATCH_ROWS, MSM_BATCH_TABLE_TERMS / n));
+  const size_t group = std::min(B, MSM_BATCH_ROWS);
+  const size_t rows0 = std::min(B, round_rows), slices0 = msm_batch_slices(rows0, n);
+  int rc;
+  if ((rc = ensure(c, L.buf[1], (shared ? n : rows0 * n) * TAB)) || (rc = ensure(c, L.buf[2], group * SUMS))) return rc;
+  if (slices0 > 1 && ((rc = ensure(c, L.buf[3], rows0 * slices0 * SUMS)) || (rc = ensure(c, L.buf[4], rows0 * 4)))) return rc;
+  u32* tables = (u32*)L.buf[1].p; u32* sums = (u32*)L.buf[2].p;
+  if (shared) hipLaunchKernelGGL(k_msm_batch_tables, dim3(blocks_for(4 * n)), dim3(256), 0, c->stream, n, (const void*)dp, tables);
+  for (size_t g0 = 0; g0 < B; g0 += group) {
+    const size_t gn = std::min(group, B - g0);
+    for (size_t r0 = g0; r0 < g0 + gn; r0 += round_rows) {
+      const size_t rows = std::min(round_rows, g0 + gn - r0), slices = msm_batch_slices(rows, n);
+      if (slices > 1 && ((rc = ensure(c, L.buf[3], rows * slices * SUMS)) || (rc = ensure(c, L.buf[4], rows * 4)))) return rc;
+      if (!shared) hipLaunchKernelGGL(k_msm_batch_tables, dim3(blocks_for(4 * rows * n)), dim3(256), 0, c->stream, rows * n, (const void*)(dp + r0 * n * 64), tables);
+      if (slices > 1) HIPCHK(c, hipMemsetAsync(L.buf[4].p, 0, rows * 4, c->stream));
+      hipLaunchKernelGGL(k_msm_batch_sum, dim3((unsigned)(rows * slices)), dim3(64), 0, c->stream, n, (u32)slices, (const void*)(ds + r0 * n * 32), (const u32*)tables,
+                         shared ? (size_t)0 : n, mp, (u32*)L.buf[3].p, (u32*)L.buf[4].p, sums + (r0 - g0) * (SUMS / 4));
+    }
+    hipLaunchKernelGGL(k_msm_batch_finish, dim3(blocks_for(gn, MSM_BATCH_FINISH_ROWS)), dim3(64), 0, c->stream, (u32)gn, mp, (const u32*)sums, (void*)(dout + g0 * 64));
+  }
+  return JJ_OK;
+}
+// rows above MSM_BATCH_MAX terms: one MSM job per row, a few in flight (the host tail of one beside the kernels of the next), results
+// through a host array
+static int msm_batch_jobs(jj_ctx* c, size_t B, size_t n, const uint8_t* scalars, const uint8_t* points, bool shared, void* out64) {
+  std::vector<uint8_t> res(B * 64);
+  std::vector<std::pair<jj_msm_job*, size_t>> q;         // jobs in flight, oldest first
+  const size_t depth = 2 * (size_t)std::max(1, c->msm_lanes);
+  int rc = JJ_OK;
+  size_t head = 0;
+  auto finish_one = [&]() { const auto& f = q[head++]; const int r = jj_msm_finish(f.first, res.data() + 64 * f.second); if (!rc) rc = r; };
+  for (size_t b = 0; b < B && !rc; b++) {
+    jj_msm_job* j = nullptr;
+    const int r = msm_begin_locked(c, n, scalars + b * n * 32, shared ? points : points + b * n * 64, 0, 1, true, &j);
+    if (r) { rc = r; break; }
+    q.emplace_back(j, b);
+    if (q.size() - head > depth) finish_one();
+  }
+  while (head < q.size()) finish_one();                   // every job is finished (and released), also after a failure
+  if (rc) return rc;
+  if (is_device_ptr(out64)) {
+    HIPCHK(c, hipMemcpyAsync(out64, res.data(), B * 64, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  } else memcpy(out64, res.data(), B * 64);
+  return JJ_OK;
+}
+JJ_API int jj_msm_batch(jj_ctx* c, size_t B, size_t n, const void* scalars, const void* points, int points_shared, void* out64) {
+  if (!c || (points_shared != 0 && points_shared != 1)) return JJ_ERR_INVALID;
+  if (B == 0) return JJ_OK;
+  if (n && (B > SIZE_MAX / n || B * n > SIZE_MAX / 64)) return JJ_ERR_INVALID;
+  if (!out64 || (n && (!scalars || !points))) return JJ_ERR_INVALID;
+  if (B > SIZE_MAX / 64) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  const bool shared = points_shared == 1;
+  if (n == 0) {
+    if (is_device_ptr(out64)) {
+      HIPCHK(c, hipMemsetAsync(out64, 0, B * 64, c->stream));
+      HIPCHK(c, hipMemset2DAsync((uint8_t*)out64 + 32, 64, 1, 1, B, c->stream));
+      return finish(c, false);
+    }
+    for (size_t b = 0; b < B; b++) memcpy((uint8_t*)out64 + 64 * b, AFFINE_IDENTITY_BYTES, 64);
+    return JJ_OK;
+  }
+  if (n > MSM_BATCH_MAX) return msm_batch_jobs(c, B, n, (const uint8_t*)scalars, (const uint8_t*)points, shared, out64);
+  int rc; OutRef o;
+  const void *ds, *dp;
+  if ((rc = stage_in(c, 0, scalars, 32 * B * n, &ds))) return rc;
+  if ((rc = stage_in(c, 1, points, 64 * (shared ? n : B * n), &dp))) return rc;
+  if ((rc = stage_out(c, c->out[0], out64, 64 * B, &o))) return rc;
+  if ((rc = msm_batch_enqueue(c, B, n, (const uint8_t*)ds, (const uint8_t*)dp, shared, (uint8_t*)o.dev))) return rc;
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
 // First half of an MSM that is cut across devices or ranks: the record of partial window sums, left where the
 // caller wants it (device memory: ready for an all_gather over RCCL; host memory: the call waits for the copy).
 //   part_index / part_count = 0 / 1   all windows of the n terms given (term partition: every rank passes its own terms)

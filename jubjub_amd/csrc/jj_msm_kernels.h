@@ -159,15 +159,8 @@ static JJ_DEV void msm_finish_window(u32* st, u32 quad, u32 role, u32 nblk, u32 
 // addition), the quads of a workgroup are folded through LDS, and the last workgroup of the window folds the workgroups' sums.  With W = 64 the windows are 3 or 4 bits wide: digits in [-8, 8].
 constexpr int SM_W = 64;                 // windows of the small-batch layout (253 = 64 * 3 + 61: 61 windows of 4 bits, 3 of 3 bits)
 constexpr int SM_SLOTS = 9;              // table entries per term: multiples 0 .. 8
-__global__ void __launch_bounds__(256) k_msm_small_tables(size_t n, const void* scalars, const void* points, MsmParams mp, u32* tables, u32* kprime, u32* counters) {
-  if (blockIdx.x == 0 && threadIdx.x < MSM_COUNTER_WORDS) counters[threadIdx.x] = 0;
-  const size_t q = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-  const u32 role = threadIdx.x & 3u;
-  if (q >= n) return;                                       // whole quads leave together
-  u32 k[8];
-  load8(k, scalars, q);
-  msm_recode(k, mp);
-  if (role == 0) store8(kprime, q, k);
+// the table {0 .. 8} P of term q, built by the four lanes of a quad (7 additions of two multiplication rounds each)
+static JJ_DEV void msm_small_table(size_t q, u32 role, const void* points, u32* tables) {
   const Affine P = load_affine(points, q);
   const ANiels pn = Curve::to_niels(P);
   Ext cur = Curve::from_affine(P);
@@ -183,6 +176,17 @@ __global__ void __launch_bounds__(256) k_msm_small_tables(size_t n, const void* 
     en.t2d = Fq::mul(T, Fq::konst(FqP::D2));
     if (role == 0) store_eniels(slot + j * ENIELS_WORDS, en);
   }
+}
+__global__ void __launch_bounds__(256) k_msm_small_tables(size_t n, const void* scalars, const void* points, MsmParams mp, u32* tables, u32* kprime, u32* counters) {
+  if (blockIdx.x == 0 && threadIdx.x < MSM_COUNTER_WORDS) counters[threadIdx.x] = 0;
+  const size_t q = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+  const u32 role = threadIdx.x & 3u;
+  if (q >= n) return;                                       // whole quads leave together
+  u32 k[8];
+  load8(k, scalars, q);
+  msm_recode(k, mp);
+  if (role == 0) store8(kprime, q, k);
+  msm_small_table(q, role, points, tables);
 }
 __global__ void __launch_bounds__(4 * MSM_TREE_QUADS) k_msm_small_sum(size_t n, MsmParams mp, u32 nblk, const u32* tables, const u32* kprime, u32* part, u32* counters, u32* rec) {
   __shared__ __attribute__((aligned(16))) u32 st[MSM_TREE_QUADS * LDS_PT_WORDS];
@@ -217,6 +221,109 @@ __global__ void __launch_bounds__(4 * MSM_TREE_QUADS) k_msm_small_sum(size_t n, 
   const u32 live = base >= n ? 0u : (n - base < MSM_TREE_QUADS ? (u32)(n - base) : (u32)MSM_TREE_QUADS);      // quads of this block that hold a term
   quad_tree_sum(st, quad, role, live, acc, T);                                            // identity when the block has no term
   msm_finish_window(st, quad, role, nblk, nblk, blk, blockIdx.y, w, acc, T, part, counters, rec);
+}
+
+// ================================================================================================ batched MSMs (jj_msm_batch)
+// B independent sums of n terms each, in the small-batch layout: the per-term tables {0 .. 8} P of k_msm_small_tables (one per
+// (row, term) for distinct points, one per term and shared by all rows otherwise: k_msm_batch_tables), 64 windows of 3-4 bits.
+// k_msm_batch_sum: ONE WAVE per (row, slice of the row's terms), ONE LANE per window.  A term's scalar is wave-uniform (one 32-byte
+// scalar load, recoded in registers: no k' buffer); every lane takes its own window's digit and reads the 144-byte entry
+// table[term][|d|] -- the 64 lanes read from the same 1296-byte table row -- and adds it into its own accumulator with the per-lane
+// formulas of the ladders (Curve::add_signed: 8 products), the next term's entry in flight meanwhile.  With few rows the terms of a row
+// are cut into slices so that rows x slices waves fill the machine; the last wave of a row to finish (a device-side counter per row)
+// adds the other slices' partial sums lane by lane.  Either way the row leaves its 64 window sums S_w in `sums`.
+// k_msm_batch_finish: one QUAD per row, 16 rows per wave: sum_w 2^(start_w) S_w by Horner (quad_dbl_t / quad_add_ext_t, as
+// k_msm_finish_dev), then 1/Z and the canonical affine bytes.  The 16 rows of a wave share one instruction stream, the inversion included.
+constexpr int MSM_BATCH_PT_WORDS = 4 * NL;             // a window sum in `sums` / `part`: U, V, Z, T = T1 T2 as NL-limb field elements
+constexpr int MSM_BATCH_FINISH_ROWS = 16;              // rows per 64-lane finish workgroup (one quad each)
+static_assert(SM_W == 64, "k_msm_batch_sum maps one lane to one window");
+static JJ_DEV void msm_batch_put(u32* dst, u32 lane, const Ext& e, const Fe& T) {
+  u32* p = dst + (size_t)lane * MSM_BATCH_PT_WORDS;
+  _Pragma("unroll") for (int l = 0; l < NL; l++) { p[l] = e.u.l[l]; p[NL + l] = e.v.l[l]; p[2 * NL + l] = e.z.l[l]; p[3 * NL + l] = T.l[l]; }
+}
+static JJ_DEV Ext msm_batch_get(const u32* src, u32 lane, Fe& T) {
+  const u32* p = src + (size_t)lane * MSM_BATCH_PT_WORDS;
+  Ext e;
+  _Pragma("unroll") for (int l = 0; l < NL; l++) { e.u.l[l] = p[l]; e.v.l[l] = p[NL + l]; e.z.l[l] = p[2 * NL + l]; T.l[l] = p[3 * NL + l]; }
+  e.t1 = e.u; e.t2 = e.v;                                  // unused: the operations that read these carry T instead
+  return e;
+}
+// table {0 .. 8} P of each of n points (no scalars: jj_msm_batch recodes them inside k_msm_batch_sum)
+__global__ void __launch_bounds__(256) k_msm_batch_tables(size_t n, const void* points, u32* tables) {
+  const size_t q = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+  if (q >= n) return;                                       // whole quads leave together
+  msm_small_table(q, threadIdx.x & 3u, points, tables);
+}
+// grid: rows x slices workgroups of 64 lanes, workgroup row * slices + slice.  scalars: rows x n x 32 bytes; tables: rows x n tables
+// (table_stride = n) or n tables shared by every row (table_stride = 0); part: rows x slices x 64 window sums (slices > 1);
+// counters: one per row, zero on entry (slices > 1); sums: rows x 64 window sums.
+__global__ void __launch_bounds__(64) k_msm_batch_sum(size_t n, u32 slices, const void* __restrict__ scalars, const u32* __restrict__ tables, size_t table_stride,
+                                                      MsmParams mp, u32* __restrict__ part, u32* __restrict__ counters, u32* __restrict__ sums) {
+  const u32 lane = threadIdx.x, row = blockIdx.x / slices, slice = blockIdx.x % slices;
+  const size_t per = (n + slices - 1) / slices, lo0 = (size_t)slice * per, lo = lo0 < n ? lo0 : n, hi = n - lo < per ? n : lo + per;
+  const uint8_t* srow = (const uint8_t*)scalars + (size_t)row * n * 32;
+  const u32* trow = tables + (size_t)row * table_stride * (SM_SLOTS * ENIELS_WORDS);
+  // digit of this lane's window in the (wave-uniform) recoded scalar of term i, and the address of its entry
+  auto entry = [&](size_t i, u32& neg) -> const u32* {
+    u32 k[8];
+    load8(k, srow, i);
+    msm_recode(k, mp);
+    const u32 a = msm_digit_reg(k, mp, (int)lane, neg);
+    return trow + (i * SM_SLOTS + a) * (size_t)ENIELS_WORDS;
+  };
+  Ext acc = Curve::identity();
+  u32 neg = 0;
+  ENiels e = Curve::eniels_identity();
+  if (lo < hi) e = load_eniels(entry(lo, neg));
+  #pragma unroll 1
+  for (size_t i = lo; i < hi; i++) {
+    const ENiels cur = e;
+    const u32 cmask = neg ? ~0u : 0u;
+    if (i + 1 < hi) e = load_eniels(entry(i + 1, neg));
+    acc = Curve::add_signed<true>(acc, cur, cmask);
+  }
+  Fe T = Curve::tt<true>(acc);
+  u32* dst = sums + (size_t)row * SM_W * MSM_BATCH_PT_WORDS;
+  if (slices > 1) {
+    __shared__ u32 last_s;
+    msm_batch_put(part + ((size_t)row * slices + slice) * SM_W * MSM_BATCH_PT_WORDS, lane, acc, T);
+    __threadfence();
+    __syncthreads();
+    if (lane == 0) last_s = atomicAdd(&counters[row], 1u) == slices - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!last_s) return;
+    __threadfence();
+    #pragma unroll 1
+    for (u32 s = 0; s < slices; s++) {
+      if (s == slice) continue;
+      Fe Tq;
+      const Ext q = msm_batch_get(part + ((size_t)row * slices + s) * SM_W * MSM_BATCH_PT_WORDS, lane, Tq);
+      acc = Curve::add<true>(acc, Curve::to_niels_t(q, Tq));
+    }
+    T = Curve::tt<true>(acc);
+  }
+  msm_batch_put(dst, lane, acc, T);
+}
+// rows x 64 window sums -> rows x 64 bytes of canonical affine points
+__global__ void __launch_bounds__(64) k_msm_batch_finish(u32 rows, MsmParams mp, const u32* __restrict__ sums, void* out64) {
+  const u32 role = threadIdx.x & 3u, row = blockIdx.x * MSM_BATCH_FINISH_ROWS + (threadIdx.x >> 2);
+  if (row >= rows) return;                                  // whole quads leave together
+  const u32* src = sums + (size_t)row * SM_W * MSM_BATCH_PT_WORDS;
+  Fe T;
+  Ext acc = msm_batch_get(src, SM_W - 1, T);
+  #pragma unroll 1
+  for (int w = SM_W - 2; w >= 0; w--) {
+    const int width = msm_win_width(mp, w);
+    #pragma unroll 1
+    for (int i = 0; i < width; i++) acc = quad_dbl_t(acc, role, T);
+    Fe Tp, dummy;
+    const Ext p = msm_batch_get(src, (u32)w, Tp);
+    acc = quad_add_ext_t(acc, T, p, Tp, role, T, Tp, Tp, dummy);
+  }
+  if (role == 0) {
+    const Fe zi = Fq::invert(acc.z);
+    store_affine(out64, row, Fq::mul(acc.u, zi), Fq::mul(acc.v, zi));
+  }
 }
 
 // ================================================================================================ Pippenger: conversion

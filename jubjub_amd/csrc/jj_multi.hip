@@ -110,6 +110,19 @@ JJ_API int jj_multi_decompress(jj_multi* m, size_t n, const void* in32, unsigned
   MultiPin pin; pin.add(in32, 32 * n); pin.add(out64, 64 * n); pin.add(ok, n);
   return multi_run(m, n, [&](jj_ctx* c, int, size_t lo, size_t hi) { return jj_decompress(c, hi - lo, U8(in32) + 32 * lo, flags, U8W(out64) + 64 * lo, ok + lo); });
 }
+// rows [g B/G, (g+1) B/G) on device g
+JJ_API int jj_multi_msm_batch(jj_multi* m, size_t B, size_t n, const void* scalars, const void* points, int points_shared, void* out64) {
+  if (!m || (points_shared != 0 && points_shared != 1)) return JJ_ERR_INVALID;
+  if (B == 0) return JJ_OK;
+  if (n && (B > SIZE_MAX / n || B * n > SIZE_MAX / 64)) return JJ_ERR_INVALID;
+  if (B > SIZE_MAX / 64 || !host_args(m, {out64}, B) || !host_args(m, {scalars, points}, n)) return JJ_ERR_INVALID;
+  const size_t pts = points_shared ? n : B * n;
+  (void)hipSetDevice(m->ctx[0]->device);
+  MultiPin pin; pin.add(scalars, 32 * B * n); pin.add(points, 64 * pts); pin.add(out64, 64 * B);
+  return multi_run(m, B, [&](jj_ctx* c, int, size_t lo, size_t hi) {
+    return hi == lo ? (int)JJ_OK : jj_msm_batch(c, hi - lo, n, U8(scalars) + 32 * n * lo, points_shared ? points : U8(points) + 64 * n * lo, points_shared, U8W(out64) + 64 * lo);
+  });
+}
 // Last step of an MSM that was cut across devices or processes: the sum of the `count` partial points (canonical
 // affine, 64 bytes each, HOST memory: what jj_msm wrote on every device / what the ranks' all_gather delivered) -> one affine
 // point.  Runs on the calling host thread with the arithmetic of the MSM's own host tail (jj_host_tail.h): a chain of `count`

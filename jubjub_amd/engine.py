@@ -55,6 +55,19 @@ class _Arg:
             self.device = None
 
 
+def _msm_batch_shapes(scalars, points):
+    """(B, n, points_shared) of jj_msm_batch's arguments: scalars (B, n, 32); points (n, 64) shared by every row or (B, n, 64)"""
+    ss, ps = tuple(scalars.shape), tuple(points.shape)
+    if len(ss) != 3 or ss[2] != 32:
+        raise ValueError("scalars: shape (B, n, 32) expected, got %r" % (ss,))
+    B, n = ss[0], ss[1]
+    if ps == (n, 64):
+        return B, n, 1
+    if ps == (B, n, 64):
+        return B, n, 0
+    raise ValueError("points: shape (%d, 64) (shared) or (%d, %d, 64) expected, got %r" % (n, B, n, ps))
+
+
 class _HostBlock:
     """owner of one jj_host_alloc block"""
 
@@ -430,6 +443,23 @@ class Engine:
     def msm(self, scalars, points):
         return self._sum_like("jj_msm", [scalars, points], [32, 64])
 
+    def msm_batch(self, scalars, points, out=None):
+        """B independent MSMs in one call (jj_msm_batch): row b = msm(scalars[b], points or points[b]).  scalars (B, n, 32); points (n, 64)
+        shared by every row or (B, n, 64); returns (B, 64).  numpy arrays or torch CUDA tensors (then on torch's current stream; up to 8192
+        terms per row the call only queues the work); `out`: a caller-owned (B, 64) array of the inputs' kind."""
+        B, n, shared = _msm_batch_shapes(scalars, points)
+        a, p = _Arg(scalars, 32), _Arg(points, 64)
+        if out is None:
+            out, optr = self._alloc(a, B, 64)
+        else:
+            oa = _Arg(out, 64)
+            if oa.n != B or oa.torch != a.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x 64 bytes of the inputs' kind expected" % B)
+            optr = oa.ptr
+        self._bind_stream([a, p])
+        self._check(self._lib.jj_msm_batch(self._ctx, C.c_size_t(B), C.c_size_t(n), a.ptr, p.ptr, C.c_int(shared), optr))
+        return out
+
     def msm_dev(self, scalars, points, out=None):
         """The same sum finished ON THE DEVICE (jj_msm_dev): no host hop, nothing waits; returns a torch uint8 tensor of 64 bytes on
         the inputs' device (torch inputs), queued on torch's current stream."""
@@ -682,4 +712,13 @@ class MultiEngine:
             raise ValueError("length mismatch")
         out = np.empty((64,), np.uint8)
         self._check(self._lib.jj_multi_msm(self._h, C.c_size_t(len(s)), sp, pp, out.ctypes.data))
+        return out
+
+    def msm_batch(self, scalars, points, out=None):
+        """jj_multi_msm_batch: Engine.msm_batch's shapes, rows cut into one contiguous block per device; host (numpy) arrays in and out"""
+        B, n, shared = _msm_batch_shapes(scalars, points)
+        s, sp = self._np(scalars, 32)
+        p, pp = self._np(points, 64)
+        out = self._out(out, (B, 64))
+        self._check(self._lib.jj_multi_msm_batch(self._h, C.c_size_t(B), C.c_size_t(n), sp, pp, C.c_int(shared), out.ctypes.data if B else None))
         return out

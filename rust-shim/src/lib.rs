@@ -132,6 +132,20 @@ impl Gpu {
         get_point(&out).into()
     }
 
+    /// `B` independent sums in one call (`jj_msm_batch`): row `b` is `sum_i points[i] * scalars[b][i]` when `points` holds `n` points shared
+    /// by every row, or `sum_i points[b n + i] * scalars[b][i]` when it holds `B n` (one run of `n` per row).  Every row has `n` scalars.
+    pub fn msm_batch(&self, points: &[AffinePoint], scalars: &[Vec<Fr>]) -> Vec<ExtendedPoint> {
+        let (b, n) = (scalars.len(), scalars.first().map_or(0, |r| r.len()));
+        assert!(scalars.iter().all(|r| r.len() == n));
+        let shared = points.len() == n;
+        assert!(shared || points.len() == b * n);
+        let flat: Vec<Fr> = scalars.iter().flatten().copied().collect();
+        let (s, p) = (put_scalars(&flat), put_points(points));
+        let mut out = vec![0u8; 64 * b];
+        assert_eq!(unsafe { jj_msm_batch(self.0, b, n, s.as_ptr() as _, p.as_ptr() as _, shared as c_int, out.as_mut_ptr() as _) }, 0);
+        out.chunks_exact(64).map(|r| get_point(r).into()).collect()
+    }
+
     /// `AffinePoint::batch_from_bytes` (src/lib.rs:541-627); `flags`: ZIP216 (from_bytes vs from_bytes_pre_zip216_compatibility,
     /// src/lib.rs:469-489), TORSION_FREE (SubgroupPoint::from_bytes, 1427-1429), NOT_SMALL_ORDER (699-705), CLEAR_COFACTOR (722-724).
     pub fn batch_from_bytes(&self, enc: &[[u8; 32]], flags: u32) -> Vec<Option<AffinePoint>> {
