@@ -212,11 +212,14 @@ int jj_point_sum(jj_ctx*, size_t n, const void* p, void* out64);
 /* out[i] = to_affine(points[i] * scalars[i])   (`ExtendedPoint * Fr`, src/lib.rs:873-879 -> 831-833 -> 357-379).
  * scalars are raw 32-byte patterns; only the low 252 bits are used, as in the reference ladder.  Results are specified for on-curve points.
  * CONSTANT-TIME like the reference's ladder (conditional_select, src/lib.rs:334-343): neither the instruction stream nor any memory
- * address depends on the scalar.  Signed 3-bit windows (k' = k + sum 4 * 8^i: 84 windows tile the 252 bits, bit 252 is the recoding carry),
- * table {P, 2P, 3P, 4P}: {P, 2P} in registers, {3P, 4P} in a per-lane LDS slot that is read whole for every window; the entry is picked
- * with bit masks, the sign applied through the subtraction formulas: 85 additions + 252 doublings.  Batches up to vb_quad_max
- * (32 768) units run one scalar multiplication per quad of lanes (every lane keeps its own coordinate of the four entries in
- * registers): same discipline, a third of the latency. */
+ * address depends on the scalar.  The x-only Montgomery ladder on the birationally equivalent curve B y^2 = x^3 + A x^2 + x (A = 40962,
+ * B = -40964): x1 = (1 + v)/(1 - v) of every base by one batch inversion per 16 units (k_varbase_mont_x1), then per bit of 251..0 one
+ * masked swap and xDBLADD (4S + 5M and a multiplication by a24 = 10240; no table, three waves per SIMD: k_varbase_mont), the y-recovery
+ * of Okeya-Sakurai and the map back to Edwards; the identity, the point of order 2 and results O, (0, -1) and -P are masked in.  Option
+ * vb_ct_window = 3 / 2 takes the Edwards ladder with signed 3- / 2-bit windows instead (k_varbase_ct3: table {P .. 4P}, {3P, 4P} in a
+ * per-lane LDS slot read whole for every window; 85 additions + 252 doublings), the same results.  Batches up to vb_quad_max (32 768)
+ * units run one scalar multiplication per quad of lanes (signed 3-bit windows, every lane keeps its own coordinate of the four entries
+ * in registers): same discipline, a third of the latency. */
 int jj_varbase_mul(jj_ctx*, size_t n, const void* scalars32, const void* points64, void* out64);
 /* same, result written as 32-byte compressed encodings (to_bytes of the product, src/lib.rs:455-464, 1419-1421) */
 int jj_varbase_mul_compressed(jj_ctx*, size_t n, const void* scalars32, const void* points64, void* out32);
@@ -224,7 +227,7 @@ int jj_varbase_mul_compressed(jj_ctx*, size_t n, const void* scalars32, const vo
 int jj_varbase_mul_ct(jj_ctx*, size_t n, const void* scalars32, const void* points64, void* out64);
 /* VARIABLE-TIME variants for PUBLIC scalars (what rounds 1-4 shipped as jj_varbase_mul): signed 5-bit windows, the lane's table
  * {0 .. 16} P in device memory, read at a digit-dependent address: a scalar-independent instruction stream but scalar-dependent
- * memory addresses (cache timing).  1.6-4.5 % faster than jj_varbase_mul at 2^20 units depending on the box (ratios 0.984 and 0.955: profiles/r5_vb_ct_window.txt, r6_vb_ct_window.txt).
+ * memory addresses (cache timing).  1.6-4.5 % faster than k_varbase_ct3 (vb_ct_window = 3) at 2^20 units depending on the box (ratios 0.984 and 0.955: profiles/r5_vb_ct_window.txt, r6_vb_ct_window.txt).
  * Nothing makes jj_varbase_mul / _compressed take this ladder: no option, no environment variable. */
 int jj_varbase_mul_vartime(jj_ctx*, size_t n, const void* scalars32, const void* points64, void* out64);
 int jj_varbase_mul_vartime_compressed(jj_ctx*, size_t n, const void* scalars32, const void* points64, void* out32);

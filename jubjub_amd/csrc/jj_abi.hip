@@ -149,13 +149,17 @@ static void varbase_geometry(jj_ctx* c, size_t n, unsigned* blocks, size_t* thre
   if (t == 0) t = 256;
   *blocks = (unsigned)(t / 256); *threads = t;
 }
-// ct: the ladder with the reference's timing discipline (no scalar-dependent address or branch): k_varbase_ct3 / k_varbase_ct_quad; otherwise the
+// ct: the ladder with the reference's timing discipline (no scalar-dependent address or branch): k_varbase_mont / _ct3 / _ct / _ct_quad; otherwise the
 // per-lane window table in memory (k_varbase / k_varbase_quad: digit-dependent addresses)
 static int varbase_to_ext(jj_ctx* c, size_t n, const void* ds, const void* dp, SoA ext, bool five, bool shared_scalar = false, bool ct = false) {
   if (ct && !five && !shared_scalar) {
     if (n <= (size_t)c->vb_quad_max) hipLaunchKernelGGL(k_varbase_ct_quad, dim3(blocks_for(4 * n)), dim3(256), 0, c->stream, n, ds, dp, ext);   // small batch: one scalar multiplication per quad of lanes
     else if (c->vb_ct_window == 3) hipLaunchKernelGGL(k_varbase_ct3, dim3(blocks_for(n)), dim3(256), CT3_LDS_BYTES_PER_BLOCK, c->stream, n, ds, dp, ext);
-    else hipLaunchKernelGGL(k_varbase_ct, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, dp, ext);
+    else if (c->vb_ct_window == 2) hipLaunchKernelGGL(k_varbase_ct, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, dp, ext);
+    else {                                                   // default: the x-only Montgomery ladder, x1 of every base batch-inverted first
+      hipLaunchKernelGGL(k_varbase_mont_x1, dim3(blocks_for(64 * ((n + 64 * MONT_X1_UNITS - 1) / (64 * MONT_X1_UNITS)))), dim3(256), 0, c->stream, n, dp, ext);
+      hipLaunchKernelGGL(k_varbase_mont, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, dp, ext);
+    }
     return JJ_OK;
   }
   if (n <= (size_t)c->vb_quad_max && !shared_scalar) {      // small batch: one scalar multiplication per quad of lanes (3x lower latency)
@@ -208,9 +212,9 @@ static int varbase_api(jj_ctx* c, size_t n, const void* scalars, const void* poi
   return finish(c, sync);
 }
 // ExtendedPoint * Fr (reference src/lib.rs:873-879 -> 357-379): the reference's ladder is constant-time (conditional_select, 334-343), and so is
-// the default here (round 5): signed 3-bit windows, mask selects, no table in memory (k_varbase_ct3; one scalar multiplication per quad of lanes up
-// to JJ_VB_QUAD_MAX units: k_varbase_ct_quad).  The _vartime entry points keep the per-lane window table in memory and signed 5-bit windows
-// (digit-dependent addresses): 1.6-4.5 % faster at 2^20 units depending on the box (profiles/r5_vb_ct_window.txt: ratio 0.984, r6_vb_ct_window.txt: 0.955), for public scalars.
+// the default here: the x-only Montgomery ladder (k_varbase_mont after k_varbase_mont_x1; vb_ct_window = 3 / 2: the signed-window Edwards
+// ladders k_varbase_ct3 / k_varbase_ct; one scalar multiplication per quad of lanes up to JJ_VB_QUAD_MAX units: k_varbase_ct_quad).  The _vartime entry points keep the per-lane window table in memory and signed 5-bit windows
+// (digit-dependent addresses): 1.6-4.5 % faster than k_varbase_ct3 at 2^20 units depending on the box (profiles/r5_vb_ct_window.txt: ratio 0.984, r6_vb_ct_window.txt: 0.955), for public scalars.
 JJ_API int jj_varbase_mul(jj_ctx* c, size_t n, const void* scalars, const void* points, void* out) { return varbase_api(c, n, scalars, points, out, 0, c && c->vb_default_ct); }
 JJ_API int jj_varbase_mul_compressed(jj_ctx* c, size_t n, const void* scalars, const void* points, void* out32) { return varbase_api(c, n, scalars, points, out32, 1, c && c->vb_default_ct); }
 JJ_API int jj_varbase_mul_ct(jj_ctx* c, size_t n, const void* scalars, const void* points, void* out) { return varbase_api(c, n, scalars, points, out, 0, true); }      // (the name rounds 3-4 gave the opt-in; always constant-time)

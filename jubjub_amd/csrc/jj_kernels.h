@@ -4,6 +4,7 @@
 // ladders, fixed-base, codec, generators), JJ_KERNELS_MSM (jj_msm.hip: jj_msm_kernels.h), JJ_KERNELS_PROBE (jj_pipeline.hip: k_peak_mad).
 #pragma once
 #include "jj_curve.h"
+#include "jj_mont.h"
 
 namespace jj {
 
@@ -630,6 +631,54 @@ __global__ void __launch_bounds__(256, 2) k_varbase_ct3(size_t n, const void* sc
   const Affine P = load_affine(points, i);
   const Ext r = varbase_ct3(P, k, slot, ext.base + i, ext.n);     // (k' is parked in the unit's limbs 0..7 of the U coordinate until the result lands there)
   ext.put(0, i, r.u); ext.put(1, i, r.v); ext.put(2, i, r.z);
+}
+#endif  // JJ_KERNELS_BATCH
+
+// The default constant-time ladder (jj_varbase_mul above vb_quad_max): the x-only ladder on the Montgomery form (jj_mont.h).  It needs the
+// affine x1 = (1 + v)/(1 - v) of every base without an inversion per lane: k_varbase_mont_x1 runs Montgomery's batch inversion over
+// MONT_X1_UNITS units per lane (units 64 apart: every step of a wave reads 64 neighbouring units) -- one inversion per 16 units -- and
+// parks x1 in the unit's Z coordinate of the output array, where k_varbase_mont reads it and later writes the result.  A zero
+// denominator (v = 1: the identity) is replaced by 1; k_varbase_mont masks that unit's result to the identity.
+#ifdef JJ_KERNELS_BATCH
+__global__ void __launch_bounds__(256) k_varbase_mont_x1(size_t n, const void* points, SoA ext) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t first = (t >> 6) * (size_t)(64 * MONT_X1_UNITS) + (t & 63u);
+  if (first >= n) return;
+  auto den_of = [&](size_t i, Fe& num) -> Fe {
+    u32 wv[8];
+    load8(wv, points, 2 * i + 1);
+    return mont_x1_den(Fq::from_words(wv), num);
+  };
+  Fe acc = Fq::one(), num;
+  #pragma unroll 1
+  for (int s = 0; s < MONT_X1_UNITS; s++) {                      // forward: prefix products, parked in the Z slots
+    const size_t i = first + (size_t)s * 64;
+    if (i >= n) break;
+    ext.put(2, i, acc);
+    acc = Fq::mul(acc, den_of(i, num));
+  }
+  Fe inv = Fq::invert(acc);
+  #pragma unroll 1
+  for (int s = MONT_X1_UNITS - 1; s >= 0; s--) {                 // backward: 1/d_s = inv * prefix_s, then inv *= d_s
+    const size_t i = first + (size_t)s * 64;
+    if (i >= n) continue;
+    const Fe d = den_of(i, num);
+    const Fe di = Fq::mul(inv, ext.get(2, i));
+    inv = Fq::mul(inv, d);
+    ext.put(2, i, Fq::mul(Fq::carry(num), di));
+  }
+}
+// 3 waves per SIMD (<= 168 VGPRs): the ladder state is five field elements and the Gray-code register, no table
+__global__ void __launch_bounds__(256, 3) k_varbase_mont(size_t n, const void* scalars, const void* points, SoA ext) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 k[8];
+  load8(k, scalars, i);
+  const Affine P = load_affine(points, i);
+  const Fe x1 = ext.get(2, i);
+  Fe u, v, z;
+  varbase_mont(P, x1, k, u, v, z);
+  ext.put(0, i, u); ext.put(1, i, v); ext.put(2, i, z);
 }
 #endif  // JJ_KERNELS_BATCH
 

@@ -132,6 +132,28 @@ class FieldModel:
         lo[-1], hi[-1] = max(lo[-1], tlo), min(hi[-1], thi)
         return V(lo, hi, a.vlo, a.vhi)
 
+    def mul_a24(self, a, k=10240, qmul=0x58549745, what="mul_a24"):
+        """mont_a24 (jj_mont.h): t_i = k a_i - qd p_i in 64 bits, qd = (a_8 qmul) >> 40 within (-2^-15, 1 + 2^-15) of k a_8 2^232 / p,
+        then one parallel carry; the top limb is bounded through the value"""
+        self._check_limbs(a, what)
+        assert max(abs(a.lo[-1]), abs(a.hi[-1])) < 1 << 26, f"{what}: top limb beyond the quotient estimate's range"
+        assert abs(qmul - k * (1 << 272) / self.p) <= 0.5
+        qd = max(abs(a.lo[-1]), abs(a.hi[-1])) * qmul // (1 << 40) + 1
+        tlo = [k * a.lo[i] - qd * self.P[i] for i in range(NL)]
+        thi = [k * a.hi[i] + qd * self.P[i] for i in range(NL)]
+        assert max(max(abs(x), abs(y)) for x, y in zip(tlo, thi)) < LIM63, f"{what}: 64-bit limb product"
+        lo, hi = [0] * NL, [MASK] * NL
+        for i in range(1, NL):
+            lo[i] += tlo[i - 1] >> LB
+            hi[i] += thi[i - 1] >> LB
+        low_lo = sum(a.lo[i] << (LB * i) for i in range(NL - 1))
+        low_hi = sum(a.hi[i] << (LB * i) for i in range(NL - 1))
+        vlo, vhi = k * low_lo - self.p, k * low_hi + 2 * self.p
+        rlo = sum(lo[i] << (LB * i) for i in range(NL - 1))
+        rhi = sum(hi[i] << (LB * i) for i in range(NL - 1))
+        lo[-1], hi[-1] = -((-(vlo - rhi)) // (1 << TOP)), (vhi - rlo) >> TOP
+        return self._check_limbs(V(lo, hi, vlo, vhi), what)
+
     def join(self, a, b):
         return V([min(x, y) for x, y in zip(a.lo, b.lo)], [max(x, y) for x, y in zip(a.hi, b.hi)], min(a.vlo, b.vlo), max(a.vhi, b.vhi))
 
@@ -359,6 +381,67 @@ def check_kernel_formulas(verbose=True):
         print("  kernel formulas (normalise, decode, sqrt, pairing, quad ops): ok")
 
 
+def check_mont_ladder(verbose=True):
+    """k_varbase_mont_x1 and k_varbase_mont (jj_mont.h): the batch inversion of 1 - v, the x-only ladder body iterated to a fixed point
+    (every coordinate of the state is a product), the y-recovery, the map to Edwards and the masked outputs"""
+    F = FieldModel(Q)
+    ONE, ZERO = F.const(MONT % Q), F.const(0)
+    unp = V([0] * NL, [MASK] * (NL - 1) + [(1 << 24) - 1], 0, (1 << 256) - 1)
+    ld = F.mul(unp, F.const((MONT * MONT) % Q), "from_words")
+    # k_varbase_mont_x1: den = 1 - v (or 1), num = 1 + v; prefix products, invert (a chain of products), x1 = carry(num) * (inv * prefix)
+    num, den = F.add(ONE, ld), F.join(F.sub(ONE, ld), ONE)
+    F.canon_ok(den, "x1.is_zero(den)")
+    acc = ONE
+    for _ in range(3):
+        acc = F.join(acc, F.mul(acc, den, "x1.prefix"))
+    chain = F.join(acc, F.mul(acc, acc, "x1.invert"))
+    chain = F.join(chain, F.mul(chain, chain, "x1.invert"))
+    inv = F.join(chain, F.mul(chain, den, "x1.inv*d"))
+    di = F.mul(inv, chain, "x1.inv*prefix")
+    x1 = F.mul(F.carry(num), di, "x1")
+    # ladder state: (1 : 0), (x1 : 1), then products; the masked swap joins the classes
+    st = F.join(F.join(ONE, ZERO), x1)
+    for it in range(80):
+        a, b = F.carry(F.add(st, st), "lad.A"), F.sub(st, st, "lad.B")
+        aa, bb = F.sqr(a, "lad.AA"), F.sqr(b, "lad.BB")
+        da, cb = F.mul(F.sub(st, st), a, "lad.DA"), F.mul(F.add(st, st), b, "lad.CB")
+        e = F.sub(aa, bb, "lad.E")
+        w = F.add(aa, F.mul_a24(e), "lad.AA+a24E")
+        outs = [F.sqr(F.carry(F.add(da, cb)), "lad.x3"), F.mul(x1, F.sqr(F.sub(da, cb), "lad.(DA-CB)^2"), "lad.z3"),
+                F.mul(e, w, "lad.z2"), F.mul(aa, bb, "lad.x2")]
+        nxt = st
+        for o in outs:
+            nxt = F.join(nxt, o)
+        if F.leq(nxt, st):
+            break
+        st = nxt
+    else:
+        raise AssertionError("Montgomery ladder state did not converge")
+    # y-recovery and the map to Edwards
+    TWO_A, TWO_B = F.const(2 * 40962 * MONT % Q), F.const(2 * (Q - 40964) * MONT % Q)
+    v1 = F.mul(x1, st, "rec.v1")
+    v3 = F.mul(F.sqr(F.sub(st, v1), "rec.v3sq"), st, "rec.v3")
+    t = F.mul(TWO_A, st, "rec.t")
+    v4 = F.add(F.mul(x1, st, "rec.x1xq"), st)
+    v2 = F.mul(F.carry(F.add(F.add(st, v1), t)), v4, "rec.v2")
+    v2 = F.mul(F.sub(v2, F.mul(t, st, "rec.tzq")), st, "rec.v2zp")
+    Y = F.mul(ld, F.sub(v2, v3), "rec.Y")
+    w = F.mul(F.mul(F.mul(TWO_B, x1, "rec.2Bx1"), st, "rec.w1"), st, "rec.w")
+    X, Z = F.mul(w, st, "rec.X"), F.mul(w, st, "rec.Z")
+    xpz = F.add(X, Z)
+    outs = [F.mul(X, xpz, "rec.U"), F.mul(Y, F.sub(X, Z), "rec.V"), F.mul(Y, xpz, "rec.W"), F.mul(ld, F.const((Q - 1) * MONT % Q), "rec.-u"),
+            ld, ONE, ZERO, F.const((Q - 1) * MONT % Q)]
+    res = outs[0]
+    for o in outs[1:]:
+        res = F.join(res, o)
+    for x in (st, x1, res):
+        F.canon_ok(x, "mont.is_zero / to_plain")
+    F.canon_ok(F.sub(ld, ONE), "mont.is_zero(v - 1)")
+    if verbose:
+        print("  ladder state: %r\n  x1: %r\n  result: %r" % (st, x1, res))
+    return st, x1, res
+
+
 def check_field_misc(p, name, verbose=True):
     F = FieldModel(p)
     unp = V([0] * NL, [MASK] * (NL - 1) + [(1 << 24) - 1], 0, (1 << 256) - 1)
@@ -387,6 +470,8 @@ def main():
     print("curve formulas (Fq):")
     check_curve()
     check_kernel_formulas()
+    print("Montgomery-form ladder (Fq):")
+    check_mont_ladder()
     print("field helpers:")
     check_field_misc(Q, "Fq")
     check_field_misc(RMOD, "Fr")

@@ -13,7 +13,7 @@ from gfx_asm import assembly  # noqa: E402
 
 
 def main():
-    want = sys.argv[1:] or ["k_varbase_ct3", "k_varbase_ct_quad", "k_varbaseILb0ELb0", "k_fixedbase_combILb1", "k_fixedbaseILb1", "k_field_opINS_3FqPELi2", "k_field_opINS_3FqPELi4"]
+    want = sys.argv[1:] or ["14k_varbase_montE", "k_varbase_ct3", "k_varbase_ct_quad", "k_varbaseILb0ELb0", "k_fixedbase_combILb1", "k_fixedbaseILb1", "k_field_opINS_3FqPELi2", "k_field_opINS_3FqPELi4"]
     asm = assembly()
     kernels = re.split(r"\n(?=_Z\w+:\s)", asm)
     for k in kernels:

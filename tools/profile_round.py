@@ -30,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (build_id, WORK)
 
-DOMINANT = {"varbase": "k_varbase_ct3", "fixedbase": "k_fixedbase_comb<", "msm": "k_msm_accumulate_seg", "decompress": "k_decompress<"}
+DOMINANT = {"varbase": "k_varbase_mont(", "fixedbase": "k_fixedbase_comb<", "msm": "k_msm_accumulate_seg", "decompress": "k_decompress<"}
 SQ_SET = "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 
 
