@@ -314,6 +314,43 @@ int jj_msm_dev(jj_ctx*, size_t n, const void* scalars32, const void* points64, v
  * run in rounds of whole rows.  n > 8192: every row is a jj_msm_begin job (device-pointer rows alternate over the context's
  * MSM lanes) finished by the host tail, and the call returns only after every row is finished, whatever the pointers. */
 int jj_msm_batch(jj_ctx*, size_t B, size_t n, const void* scalars32, const void* points64, int points_shared, void* out64);
+/* Fixed-basis MSM: many scalar vectors against ONE set of points that is handed over once (Pedersen vector commitments, value / note
+ * commitments over many generators, an IPA prover, a batch verifier with a fixed key set) -- the MSM's counterpart of
+ * jj_fixedbase_table_create / jj_fixedbase_mul.  jj_msm_basis_create copies the n points (host or device pointer; the caller's array may be
+ * freed or overwritten when the call returns) into tables in device memory, jj_msm_basis_mul brings scalars only:
+ *   rows b < B:  out64[b] = to_affine(sum_{i < m} points[i] * scalars32[b][i]),   m <= n: the FIRST m points of the basis
+ * scalars32: B x m x 32 bytes, raw patterns, low 252 bits used; every row equals jj_msm(ctx, m, row, first m points) byte for byte (exact on
+ * the whole curve: cofactor components, the identity, scalars >= r).  VARIABLE-TIME like jj_msm.
+ *   mode 1 (points)   the converted points stay resident, 128 bytes per point: jj_msm's plan without the copy and the conversion of the points
+ *   mode 2 (windows)  additionally 2^(start_w) P_i for every window w of the basis's layout, 128 bytes x windows per point: digit w of a scalar
+ *                     selects row (w, i) and ALL windows add into one bucket set -- one bucket reduce instead of one per window, a record of
+ *                     one point, no Horner chain on the host (one inversion)
+ *   mode 0 (auto)     the faster of the two as measured (profiles/msm_basis_ab.txt) whose tables fit HALF of the device memory that is
+ *                     free at create: today mode 1 for every n -- with jj_msm's window counts mode 2 measured 5-9 % slower, it is an opt-in
+ *   windows           0 = what jj_msm takes for n terms (23 / 17 / 16), else 16 .. 36: the layout of the table (mode 2; fixed at create, also
+ *                     for shorter prefixes) or of every call (mode 1; 0 there: chosen per call from m, option msm_windows included).
+ *                     Out of range: JJ_ERR_INVALID.  Ignored for rows of up to 8192 terms.
+ * Rows of up to 8192 terms (the limit of jj_msm_batch's batched kernels) run over per-point tables {0 .. 8} P (1296 bytes per point) that
+ * every basis keeps for its first min(n, 8192) points, in both modes alike: for B > 1 a few launches on the context's stream whatever B is (with
+ * device pointers the call only queues that work and returns); a single row takes jj_msm's small-batch pass over the tables and its host tail.  Longer rows are one Pippenger pass each over the resident records, several in
+ * flight over the context's MSM lanes when B > 1, each finished by the host tail: the call then returns after every row is finished, whatever
+ * the pointers (a device out64 is written by a copy the call waits for when B > 1, by a queued copy when B = 1, as jj_msm).  With any host
+ * pointer the results are in memory on return.
+ * B = 0 succeeds and touches nothing; m = 0 (also a basis of n = 0 points) writes the identity (0, 1) to every row.  JJ_ERR_INVALID, before any
+ * device work: a NULL context or basis, NULL where a size is non-zero, m > n, an unknown mode, B * m * 32 beyond size_t, n above 2^24.
+ * JJ_ERR_NOMEM: the tables do not fit (nothing is left behind).  A basis lives in the memory of the device of the context that built it and
+ * serves every context of that device, from several threads at once; a context of another device gets JJ_ERR_INVALID.  Destroy it before the
+ * last context of its device.
+ * jj_msm_basis_info: out[0] = n, out[1] = mode in use (1 | 2; for at most 8192 points the mode asked for, 1 for auto), out[2] = windows of the
+ * layout (64 for at most 8192 points), out[3] = bytes of device memory held.
+ * jj_plan_msm_basis: what create chooses for n points when budget_bytes of device memory may be used -- a pure function (no context, no
+ * device): out[0] = mode, out[1] = windows, out[2] = table bytes, out[3] = route of an n-term row (0 small tables, 1 Pippenger). */
+typedef struct jj_msm_basis jj_msm_basis;
+int jj_msm_basis_create(jj_ctx*, size_t n, const void* points64, int mode, int windows, jj_msm_basis** out);
+int jj_msm_basis_destroy(jj_ctx*, jj_msm_basis* basis);
+int jj_msm_basis_info(const jj_msm_basis* basis, int64_t out[4]);
+int jj_msm_basis_mul(jj_ctx*, const jj_msm_basis* basis, size_t B, size_t m, const void* scalars32, void* out64);
+int jj_plan_msm_basis(size_t n, int mode, int windows, uint64_t budget_bytes, int64_t out[4]);
 /* MSM cut across devices or ranks.  jj_msm_partial leaves the RECORD of partial window sums instead of the
  * point: JJ_MSM_PARTIAL_BYTES bytes (64-byte header: magic, version, number of windows W, 1, bit mask of the windows
  * present, n; then one 128-byte point per window: U, V, Z and T = T1 T2, each the 256-bit little-endian integer of

@@ -320,6 +320,41 @@ inline AffineBatch msm_batch(const Context& c, const std::vector<AffineBatch>& p
   return AffineBatch(c, std::move(out));
 }
 
+// Many scalar vectors against ONE set of points (jj_msm_basis_*): the points go to the device once (tables owned by this object), every
+// msm(basis, rows) brings scalars only.  Mode: 0 = auto, 1 = points, 2 = windows; windows: 0 = auto or 16 .. 36 (jubjub_hip.h).
+class MsmBasis {
+ public:
+  MsmBasis(const Context& c, const AffineBatch& points, int mode = 0, int windows = 0) : c_(&c), n_(points.len()) {
+    c.check(jj_msm_basis_create(c.raw(), n_, points.coords().data(), mode, windows, &b_));
+  }
+  MsmBasis(const MsmBasis&) = delete;
+  MsmBasis& operator=(const MsmBasis&) = delete;
+  ~MsmBasis() { if (b_) (void)jj_msm_basis_destroy(c_->raw(), b_); }
+  size_t len() const { return n_; }
+  const jj_msm_basis* raw() const { return b_; }
+  const Context& context() const { return *c_; }
+  // {n, mode in use, windows of the layout, bytes of device memory}
+  std::vector<int64_t> info() const { std::vector<int64_t> v(4); c_->check(jj_msm_basis_info(b_, v.data())); return v; }
+ private:
+  const Context* c_;
+  size_t n_;
+  jj_msm_basis* b_ = nullptr;
+};
+// row b = sum_{i < m} basis point i * rows[b][i]; every row has the same length m <= basis.len()
+inline AffineBatch msm(const MsmBasis& basis, const std::vector<FrBatch>& rows) {
+  const Context& c = basis.context();
+  const size_t m = rows.empty() ? 0 : rows[0].len();
+  std::vector<Bytes32> flat;
+  flat.reserve(rows.size() * m);
+  for (const FrBatch& s : rows) {
+    if (s.len() != m) throw Error(JJ_ERR_INVALID, "length mismatch");
+    flat.insert(flat.end(), s.to_bytes().begin(), s.to_bytes().end());
+  }
+  std::vector<Bytes64> out(rows.size());
+  c.check(jj_msm_basis_mul(c.raw(), basis.raw(), rows.size(), m, flat.data(), out.data()));
+  return AffineBatch(c, std::move(out));
+}
+
 // The same sum with the host tail of one MSM overlapping the kernels of the next (jj_msm_begin / jj_msm_finish): the job owns copies
 // of its inputs until it is finished
 struct AllRanks { bool by_windows = false; };      // MsmJob over every rank of the communicator lent with set_comm (jj_msm_allgather_begin)

@@ -22,8 +22,12 @@ static void msm_layout(MsmParams& mp, int W, int w0, int wstride) {
 // from this many terms the large-input configuration (17 / 16 windows, length-sorted segments) is faster than 23 windows + chunks + fix-up
 // (experiments/misc/msm_crossover.py: 131 072 terms 0.438 against 0.448 ms, 150 000 terms 0.485 against 0.459 ms, 235 000 terms 0.727 against 0.533 ms)
 constexpr size_t MSM_LARGE_MIN = (size_t)9 << 14;
+static int msm_windows_default(size_t n);
 static int msm_windows_for(jj_ctx* c, size_t n) {
   if (c->msm_windows >= MSM_WINDOWS_MIN && c->msm_windows <= MSM_WINDOWS_MAX) return c->msm_windows;
+  return msm_windows_default(n);
+}
+static int msm_windows_default(size_t n) {
   // measured (experiments/misc/msm_sweep*.sh, profiles/r3_msm_window_sweep.txt, r3_msm_reduce_grid.txt): 16 windows (13 of 16 bits, 3 of
   // 15) from 2^18 terms (round 6; from 2^20 before: with the two-level reduce -- 8 level-1 rows -- the 2^15 buckets per window no longer cost
   // a 210 us chain, and 16 windows beat 17 by 0.5 % at 2^18 and 2 % at 2^19 terms, profiles/r5_msm_mid_sweep.txt); 17 windows (15 of 15 bits,
@@ -49,16 +53,24 @@ static int msm_enqueue_small(jj_ctx* c, MsmLane& L, size_t n, const void* ds, co
   return JJ_OK;
 }
 
-static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* ds, const void* dp, int part_w0, int part_stride, void* rec_dev) {
+// A pass over the resident records of a basis (jj_msm_basis_*) instead of the caller's points: `niels` replaces the lane's own array and no
+// kernel converts points; W = the windows of the basis's layout (0: as jj_msm picks them); slot_stride > 0: the array is a WINDOW TABLE with
+// row (w, i) at w * slot_stride + i -- the scatter writes that row into the sort's entries, every slot accumulates into its own bucket set as
+// before, k_msm_fold_slots adds the sets into slot 0 and the reduce runs as a pass that owns window 0 alone (a record of one point).
+struct MsmTab { const u32* niels; size_t slot_stride; int W; };
+static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* ds, const void* dp, int part_w0, int part_stride, void* rec_dev, const MsmTab* tab = nullptr) {
   MsmParams mp;
-  msm_layout(mp, msm_windows_for(c, n), part_w0, part_stride);
-  const u32 B = mp.B, Ws = (u32)mp.Ws;
+  msm_layout(mp, tab && tab->W ? tab->W : msm_windows_for(c, n), part_w0, part_stride);
+  const bool folded = tab && tab->slot_stride;
+  MsmParams mpr = mp;                                                     // the layout of the reduce: the pass's own, or window 0 alone over the folded set
+  if (folded) msm_layout(mpr, mp.W, 0, mp.W);
+  const u32 B = mp.B, Ws = (u32)mp.Ws, Wr = (u32)mpr.Ws;
   const size_t nb = (size_t)Ws * B;
   // buckets per reduce chunk: a quad walks L buckets (2 L additions), then ~2 c operations multiply by the chunk's first index, and
   // every workgroup of 64 quads is one wave per SIMD of a CU.  The chains are bound by the instructions a wave issues, and a
   // second workgroup on a CU slows both by ~1.6x, so: the smallest L (at least 4) for which the workgroups that have chunks fit
   // one per CU.  JJ_MSM_REDUCE_CHUNK overrides; never more than one window.
-  auto reduce_blocks = [&](u32 l) { const u32 nk = std::min<u32>(MSM_TREE_QUADS, (B / l + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS); u32 t = 0; for (u32 s = 0; s < Ws; s++) t += msm_reduce_blocks(mp, (int)s, l, nk); return t; };
+  auto reduce_blocks = [&](u32 l) { const u32 nk = std::min<u32>(MSM_TREE_QUADS, (B / l + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS); u32 t = 0; for (u32 s = 0; s < Wr; s++) t += msm_reduce_blocks(mpr, (int)s, l, nk); return t; };
   u32 L_auto = 4;
   while (L_auto < B && reduce_blocks(L_auto) > (u32)c->cus) L_auto <<= 1;
   const u32 L = std::min<u32>(c->msm_reduce_chunk ? (u32)c->msm_reduce_chunk : L_auto, B);
@@ -72,7 +84,7 @@ static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* d
   u32 l1_rows = 0;
   if (c->msm_l1_rows > 0) l1_rows = (u32)c->msm_l1_rows;
   else if (c->msm_l1_rows < 0 && B >= 16384) l1_rows = B >= 32768 ? 8 : 4;
-  const u32 Bmin = mp.r ? B / 2 : B;                                     // buckets of the narrowest window of the layout
+  const u32 Bmin = mp.r && !folded ? B / 2 : B;                           // buckets of the narrowest window of the layout (folded: window 0, the widest)
   while (l1_rows > 1 && (l1_rows > Bmin || B / l1_rows < 64)) l1_rows >>= 1;     // every window has at least one row; whole waves per window
   if (l1_rows < 2) l1_rows = 0;
   int mbits = 0; u32 L2 = 0, nblk2 = 0;
@@ -80,11 +92,11 @@ static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* d
     const u32 M = B / l1_rows;
     while ((1u << mbits) < M) mbits++;
     L2 = 4;
-    while (L2 < M && ((u64)Ws * ((M / L2 + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS) > (u64)c->cus || (M / L2 + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS > (u32)MSM_TREE_QUADS)) L2 <<= 1;
+    while (L2 < M && ((u64)Wr * ((M / L2 + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS) > (u64)c->cus || (M / L2 + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS > (u32)MSM_TREE_QUADS)) L2 <<= 1;
     if (c->msm_l2_chunk && (u32)c->msm_l2_chunk <= M && (M / (u32)c->msm_l2_chunk + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS <= (u32)MSM_TREE_QUADS) L2 = (u32)c->msm_l2_chunk;
     nblk2 = (M / L2 + MSM_TREE_QUADS - 1) / MSM_TREE_QUADS;
   }
-  const size_t l1_bytes = l1_rows ? (size_t)Ws * (B / l1_rows) * ENIELS_WORDS * 4 : 0;      // one array of extended-Niels records (S, then T)
+  const size_t l1_bytes = l1_rows ? (size_t)Wr * (B / l1_rows) * ENIELS_WORDS * 4 : 0;      // one array of extended-Niels records (S, then T)
   int rc;
   DevBuf &kprime = ln.buf[0], &niels = ln.buf[1], &offb = ln.buf[2], &idx = ln.buf[3], &buckets = ln.buf[4], &ra = ln.buf[5], &tcnt = ln.buf[7];
   // Entries per lane of the chunked accumulation (below MSM_LARGE_MIN terms; above, the segments decide).  The launch is Ws x ceil(nchunk / 256)
@@ -123,7 +135,7 @@ static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* d
   const size_t max_segs = nb + (n * (size_t)Ws) / P + 1;
   const size_t bh_words = (size_t)stiles * (P + 1), hdr_words = bh_words + 2 * (P + 2) + 16;
   if ((rc = ensure(c, kprime, n * 32))) return rc;
-  if ((rc = ensure(c, niels, n * (size_t)GNIELS_WORDS * 4))) return rc;
+  if (!tab && (rc = ensure(c, niels, n * (size_t)GNIELS_WORDS * 4))) return rc;
   if ((rc = ensure(c, offb, (size_t)Ws * (B + 1) * 4))) return rc;
   if ((rc = ensure(c, idx, n * (size_t)Ws * 4))) return rc;
   if ((rc = ensure(c, tcnt, two_pass ? ((size_t)Ws * (2 * pm + 1)) * 4 : front1 ? (size_t)Ws * f2_parts * B * 4 : (size_t)Ws * ntiles * B * 4))) return rc;
@@ -139,6 +151,8 @@ static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* d
   u32* counters = (u32*)ln.ctl.p;                          // cleared by the sort's plan kernel
   BigBucket* big = (BigBucket*)((uint8_t*)ln.ctl.p + MSM_BIG_OFF);
   u32* part = (u32*)((uint8_t*)ln.ctl.p + MSM_PART_OFF);
+  const u32* nl = tab ? tab->niels : (const u32*)niels.p;                    // the records the accumulation gathers
+  const size_t ts = folded ? tab->slot_stride : 0;
   // One conversion launch for scalars and points.  (Rounds 2-3 ran the point half on a second stream beside the sort from 2^18
   // terms; with the entries staged through LDS the conversion is short enough that the fork, its two events and the contention
   // with the sort's first kernel cost more than the overlap returns: 2^18 terms 0.565 -> 0.556 ms, 2^20 1.262 -> 1.254 ms.)
@@ -147,7 +161,7 @@ static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* d
   // round-4 kernels (per-tile counts + a scan: the order of the entries inside a bucket is then the order of the terms).
   // (measured, experiments/misc/msm_sort_hist_ab.py, three boxes: 2^20 terms -3 ... -7 % (1.32 -> 1.24 ms), 2^19 -1 ... -4 %, 2^18 and 2^21 0 ... -2 %, 2^22 +0.7 ... -1.5 %:
   // at 2^22 terms the 8192 tiles' atomics on the same 2048 cursors cost about what the histogram pass they replace costs, so the fused form stops at 3 x 2^20 terms)
-  const bool fused_hist = two_pass && c->msm_fused_hist && Ws <= 64 && Ws * HB <= 4096 && n <= ((size_t)3 << 20);
+  const bool fused_hist = !tab && two_pass && c->msm_fused_hist && Ws <= 64 && Ws * HB <= 4096 && n <= ((size_t)3 << 20);
   if (fused_hist) {
     const bool fresh = ln.bins.cap == 0;
     if ((rc = ensure(c, ln.bins, (size_t)2 * 2 * MSM_BINS_WORDS * 4))) return rc;
@@ -167,25 +181,30 @@ static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* d
     if (seg_fused) hipLaunchKernelGGL(k_msm_part_sort<true>, dim3(HB, Ws), dim3(MSM_P2_THREADS), 0, st, mp, (u32)n, (const u32*)nullptr, (const u32*)rec, (const uint8_t*)lo8, (u32*)idx.p, off, P, ExtAoS{(u32*)buckets.p}, (u32*)ln.seg.p, (const u32*)totals);
     else hipLaunchKernelGGL(k_msm_part_sort<false>, dim3(HB, Ws), dim3(MSM_P2_THREADS), 0, st, mp, (u32)n, (const u32*)nullptr, (const u32*)rec, (const uint8_t*)lo8, (u32*)idx.p, off, P, ExtAoS{nullptr}, (u32*)nullptr, (const u32*)totals);
   } else if (two_pass) {
-    hipLaunchKernelGGL(k_msm_convert, dim3(blocks_for(n)), dim3(256), 0, st, n, ds, dp, mp, (u32*)kprime.p, (u32*)niels.p, 3);
+    // (a basis: the scalars alone, and the separate histogram kernels -- the fused one converts points on its way)
+    hipLaunchKernelGGL(k_msm_convert, dim3(blocks_for(n)), dim3(256), 0, st, n, ds, dp, mp, (u32*)kprime.p, (u32*)niels.p, tab ? 1 : 3);
     u32* tc = (u32*)tcnt.p; u32* tcs = tc + (size_t)Ws * pm;
     u32* rec = (u32*)ra.p; uint8_t* lo8 = (uint8_t*)ra.p + n * (size_t)Ws * 4;     // the head buffer is free until the accumulation
     hipLaunchKernelGGL(k_msm_part_hist, dim3(ptiles, Ws), dim3(MSM_SORT_THREADS), 0, st, n, (size_t)MSM_P1_TILE, mp, (const u32*)kprime.p, tc);
     hipLaunchKernelGGL(k_msm_part_plan, dim3(Ws), dim3(1024), 0, st, n, (u32)pm, (const u32*)tc, tcs, counters);
-    hipLaunchKernelGGL(k_msm_part_scatter, dim3(ptiles, Ws), dim3(MSM_SORT_THREADS), 0, st, n, (size_t)MSM_P1_TILE, mp, (const u32*)kprime.p, (const u32*)tcs, rec, lo8, (const u32*)nullptr, (u32*)nullptr);
+    if (folded) hipLaunchKernelGGL(k_msm_part_scatter_tab, dim3(ptiles, Ws), dim3(MSM_SORT_THREADS), 0, st, n, (size_t)MSM_P1_TILE, mp, (const u32*)kprime.p, (const u32*)tcs, rec, lo8, (const u32*)nullptr, (u32*)nullptr, ts);
+    else hipLaunchKernelGGL(k_msm_part_scatter, dim3(ptiles, Ws), dim3(MSM_SORT_THREADS), 0, st, n, (size_t)MSM_P1_TILE, mp, (const u32*)kprime.p, (const u32*)tcs, rec, lo8, (const u32*)nullptr, (u32*)nullptr);
     if (seg_fused) hipLaunchKernelGGL(k_msm_part_sort<true>, dim3(HB, Ws), dim3(MSM_P2_THREADS), 0, st, mp, ptiles, (const u32*)tcs, (const u32*)rec, (const uint8_t*)lo8, (u32*)idx.p, off, P, ExtAoS{(u32*)buckets.p}, (u32*)ln.seg.p, (const u32*)nullptr);
     else hipLaunchKernelGGL(k_msm_part_sort<false>, dim3(HB, Ws), dim3(MSM_P2_THREADS), 0, st, mp, ptiles, (const u32*)tcs, (const u32*)rec, (const uint8_t*)lo8, (u32*)idx.p, off, P, ExtAoS{nullptr}, (u32*)nullptr, (const u32*)nullptr);
   } else if (front1) {
     // round 6: counting (from the raw scalars) + point conversion in one launch, plan + scatter in the next (k_msm_front2 / k_msm_scatter2); no k'
     const size_t f2_lds = std::max<size_t>((size_t)B * 4, (size_t)MSM_F2_STAGE_WORDS * 4);
     if (!c->msm_front1_lds_set) { HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_front2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>((size_t)4096 * 4, (size_t)MSM_F2_STAGE_WORDS * 4))); c->msm_front1_lds_set = true; }
-    hipLaunchKernelGGL(k_msm_front2, dim3(f2_parts * Ws + (unsigned)((n + MSM_F2_THREADS - 1) / MSM_F2_THREADS)), dim3(MSM_F2_THREADS), f2_lds, st, n, ds, dp, mp, (u32*)niels.p, (u32*)tcnt.p, counters, f2_parts, f2_part_terms);
-    hipLaunchKernelGGL(k_msm_scatter2, dim3(f2_parts * 8 * ((Ws + 7) / 8)), dim3(MSM_SORT_THREADS), B * 4, st, n, f2_parts, f2_part_terms, mp, ds, (const u32*)tcnt.p, off, (u32*)idx.p);
+    // (a basis: the counting workgroups alone -- the grid ends before the workgroups that convert points)
+    hipLaunchKernelGGL(k_msm_front2, dim3(f2_parts * Ws + (tab ? 0u : (unsigned)((n + MSM_F2_THREADS - 1) / MSM_F2_THREADS))), dim3(MSM_F2_THREADS), f2_lds, st, n, ds, dp, mp, (u32*)niels.p, (u32*)tcnt.p, counters, f2_parts, f2_part_terms);
+    if (folded) hipLaunchKernelGGL(k_msm_scatter2_tab, dim3(f2_parts * 8 * ((Ws + 7) / 8)), dim3(MSM_SORT_THREADS), B * 4, st, n, f2_parts, f2_part_terms, mp, ds, (const u32*)tcnt.p, off, (u32*)idx.p, ts);
+    else hipLaunchKernelGGL(k_msm_scatter2, dim3(f2_parts * 8 * ((Ws + 7) / 8)), dim3(MSM_SORT_THREADS), B * 4, st, n, f2_parts, f2_part_terms, mp, ds, (const u32*)tcnt.p, off, (u32*)idx.p);
   } else {
-    hipLaunchKernelGGL(k_msm_convert, dim3(blocks_for(n)), dim3(256), 0, st, n, ds, dp, mp, (u32*)kprime.p, (u32*)niels.p, 3);
+    hipLaunchKernelGGL(k_msm_convert, dim3(blocks_for(n)), dim3(256), 0, st, n, ds, dp, mp, (u32*)kprime.p, (u32*)niels.p, tab ? 1 : 3);
     hipLaunchKernelGGL(k_msm_hist, dim3(ntiles, Ws), dim3(MSM_SORT_THREADS), B * 4, st, n, tile, mp, (const u32*)kprime.p, (u32*)tcnt.p);
     hipLaunchKernelGGL(k_msm_plan, dim3(Ws), dim3(1024), 0, st, n, B, ntiles, (u32*)tcnt.p, off, counters);
-    hipLaunchKernelGGL(k_msm_scatter, dim3(ntiles * 8 * ((Ws + 7) / 8)), dim3(MSM_SORT_THREADS), B * 4, st, n, tile, ntiles, mp, (const u32*)kprime.p, (const u32*)tcnt.p, (u32*)idx.p);
+    if (folded) hipLaunchKernelGGL(k_msm_scatter_tab, dim3(ntiles * 8 * ((Ws + 7) / 8)), dim3(MSM_SORT_THREADS), B * 4, st, n, tile, ntiles, mp, (const u32*)kprime.p, (const u32*)tcnt.p, (u32*)idx.p, ts);
+    else hipLaunchKernelGGL(k_msm_scatter, dim3(ntiles * 8 * ((Ws + 7) / 8)), dim3(MSM_SORT_THREADS), B * 4, st, n, tile, ntiles, mp, (const u32*)kprime.p, (const u32*)tcnt.p, (u32*)idx.p);
   }
   const ExtAoS head{(u32*)ra.p}, bk{(u32*)buckets.p};
   SoA partial = soa_of(ln.bigpart, (size_t)FIXUP_BIG_MAX * FIXUP_BIG_QUADS);
@@ -197,21 +216,27 @@ static int msm_enqueue_pippenger(jj_ctx* c, MsmLane& ln, size_t n, const void* d
     if (!seg_fused) hipLaunchKernelGGL(k_seg_hist, dim3(stiles), dim3(256), 0, st, nb, B, per_tile, P, (const u32*)off, bk, bh);
     hipLaunchKernelGGL(k_seg_plan, dim3(P + 1), dim3(256), 0, st, stiles, bh, soff);
     hipLaunchKernelGGL(k_seg_scatter, dim3(stiles), dim3(256), 0, st, nb, B, per_tile, P, (const u32*)off, (const u32*)bh, (const u32*)soff, soff + (P + 1), seg, counters, merge, big);
-    hipLaunchKernelGGL(k_msm_accumulate_seg, dim3(blocks_for(max_segs)), dim3(256), 0, st, (const u32*)(soff + (P + 1)), (const Seg*)seg, (const u32*)idx.p, (const u32*)niels.p, bk, head);
+    hipLaunchKernelGGL(k_msm_accumulate_seg, dim3(blocks_for(max_segs)), dim3(256), 0, st, (const u32*)(soff + (P + 1)), (const Seg*)seg, (const u32*)idx.p, nl, bk, head);
     merge_list = merge;
   } else {
-    if (B <= MSM_ACC_LDS_BUCKETS && c->msm_acc_lds) hipLaunchKernelGGL(k_msm_accumulate<true>, dim3(blocks_for(nchunk), Ws), dim3(256), (B + 1) * 4, st, n, B, chunk, nchunk, (const u32*)off, (const u32*)idx.p, (const u32*)niels.p, bk, head);
-    else hipLaunchKernelGGL(k_msm_accumulate<false>, dim3(blocks_for(nchunk), Ws), dim3(256), 0, st, n, B, chunk, nchunk, (const u32*)off, (const u32*)idx.p, (const u32*)niels.p, bk, head);
+    if (B <= MSM_ACC_LDS_BUCKETS && c->msm_acc_lds) hipLaunchKernelGGL(k_msm_accumulate<true>, dim3(blocks_for(nchunk), Ws), dim3(256), (B + 1) * 4, st, n, B, chunk, nchunk, (const u32*)off, (const u32*)idx.p, nl, bk, head);
+    else hipLaunchKernelGGL(k_msm_accumulate<false>, dim3(blocks_for(nchunk), Ws), dim3(256), 0, st, n, B, chunk, nchunk, (const u32*)off, (const u32*)idx.p, nl, bk, head);
     hipLaunchKernelGGL(k_msm_fixup, dim3(blocks_for(2 * nb)), dim3(256), 0, st, n, B, Ws, chunk, nchunk, (const u32*)off, bk, head);      // (big buckets included: no second launch)
   }
   // (segment path: 512 workgroups, the merge list of repeated scalars is walked by the same launch as the big buckets)
   if (use_segments) hipLaunchKernelGGL(k_msm_fixup_big, dim3(2u * (unsigned)c->cus), dim3(256), 0, st, counters, (const BigBucket*)big, bk, head, partial, merge_list);
+  if (folded && Ws > 1) {
+    // lanes per bucket: as many (up to 8) as keep the launch within about two waves per SIMD
+    u32 fp = 8;
+    while (fp > 1 && (size_t)B * fp > (size_t)c->cus * 512) fp >>= 1;
+    hipLaunchKernelGGL(k_msm_fold_slots, dim3(blocks_for((size_t)B * fp)), dim3(256), 0, st, B, Ws, fp, bk);
+  }
   if (l1_rows) {
     u32* SN = (u32*)ra.p; u32* TN = (u32*)((uint8_t*)ra.p + l1_bytes);        // the heads are dead: k_msm_fixup_big was their last reader
-    hipLaunchKernelGGL(k_msm_reduce_l1, dim3(blocks_for((size_t)Ws << mbits)), dim3(256), 0, st, mp, mbits, bk, SN, TN);
-    hipLaunchKernelGGL(k_msm_reduce_l2, dim3(Ws * nblk2), dim3(4 * MSM_TREE_QUADS), 0, st, n, mp, mbits, L2, nblk2, (const u32*)SN, (const u32*)TN, part, counters, (u32*)rec_dev);
-  } else if (K > MSM_TREE_QUADS * nblk) hipLaunchKernelGGL(k_msm_reduce_fold<true>, dim3(reduce_grid), dim3(4 * MSM_TREE_QUADS), 0, st, n, mp, L, nblk, jbits, bk, part, counters, (u32*)rec_dev);
-  else hipLaunchKernelGGL(k_msm_reduce_fold<false>, dim3(reduce_grid), dim3(4 * MSM_TREE_QUADS), 0, st, n, mp, L, nblk, jbits, bk, part, counters, (u32*)rec_dev);
+    hipLaunchKernelGGL(k_msm_reduce_l1, dim3(blocks_for((size_t)Wr << mbits)), dim3(256), 0, st, mpr, mbits, bk, SN, TN);
+    hipLaunchKernelGGL(k_msm_reduce_l2, dim3(Wr * nblk2), dim3(4 * MSM_TREE_QUADS), 0, st, n, mpr, mbits, L2, nblk2, (const u32*)SN, (const u32*)TN, part, counters, (u32*)rec_dev);
+  } else if (K > MSM_TREE_QUADS * nblk) hipLaunchKernelGGL(k_msm_reduce_fold<true>, dim3(reduce_grid), dim3(4 * MSM_TREE_QUADS), 0, st, n, mpr, L, nblk, jbits, bk, part, counters, (u32*)rec_dev);
+  else hipLaunchKernelGGL(k_msm_reduce_fold<false>, dim3(reduce_grid), dim3(4 * MSM_TREE_QUADS), 0, st, n, mpr, L, nblk, jbits, bk, part, counters, (u32*)rec_dev);
   return JJ_OK;
 }
 // one pass (at most 2^24 terms: 32-bit sort indices), record left at rec_dev
@@ -429,7 +454,8 @@ static size_t msm_batch_slices(size_t rows, size_t n) {
 }
 // rows [0, B) of device arrays -> out (device), all on the context's stream.  Workspaces of lane 0 (ordered with jj_msm by the stream):
 // buf[1] tables, buf[2] window sums, buf[3] slice partials, buf[4] per-row counters
-static int msm_batch_enqueue(jj_ctx* c, size_t B, size_t n, const uint8_t* ds, const uint8_t* dp, bool shared, uint8_t* dout) {
+// resident: the tables {0 .. 8} P of a basis (jj_msm_basis_*), shared by all rows: no table launch, no table workspace
+static int msm_batch_enqueue(jj_ctx* c, size_t B, size_t n, const uint8_t* ds, const uint8_t* dp, bool shared, uint8_t* dout, const u32* resident = nullptr) {
   MsmLane& L = c->lanes[0];
   MsmParams mp;
   msm_layout(mp, SM_W, 0, 1);
@@ -438,10 +464,10 @@ static int msm_batch_enqueue(jj_ctx* c, size_t B, size_t n, const uint8_t* ds, c
   const size_t group = std::min(B, MSM_BATCH_ROWS);
   const size_t rows0 = std::min(B, round_rows), slices0 = msm_batch_slices(rows0, n);
   int rc;
-  if ((rc = ensure(c, L.buf[1], (shared ? n : rows0 * n) * TAB)) || (rc = ensure(c, L.buf[2], group * SUMS))) return rc;
+  if ((!resident && (rc = ensure(c, L.buf[1], (shared ? n : rows0 * n) * TAB))) || (rc = ensure(c, L.buf[2], group * SUMS))) return rc;
   if (slices0 > 1 && ((rc = ensure(c, L.buf[3], rows0 * slices0 * SUMS)) || (rc = ensure(c, L.buf[4], rows0 * 4)))) return rc;
-  u32* tables = (u32*)L.buf[1].p; u32* sums = (u32*)L.buf[2].p;
-  if (shared) hipLaunchKernelGGL(k_msm_batch_tables, dim3(blocks_for(4 * n)), dim3(256), 0, c->stream, n, (const void*)dp, tables);
+  u32* tables = resident ? const_cast<u32*>(resident) : (u32*)L.buf[1].p; u32* sums = (u32*)L.buf[2].p;
+  if (shared && !resident) hipLaunchKernelGGL(k_msm_batch_tables, dim3(blocks_for(4 * n)), dim3(256), 0, c->stream, n, (const void*)dp, tables);
   for (size_t g0 = 0; g0 < B; g0 += group) {
     const size_t gn = std::min(group, B - g0);
     for (size_t r0 = g0; r0 < g0 + gn; r0 += round_rows) {
@@ -507,6 +533,198 @@ JJ_API int jj_msm_batch(jj_ctx* c, size_t B, size_t n, const void* scalars, cons
   bool sync = false;
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
+}
+// ---- fixed-basis MSM (jj_msm_basis_*): the points are handed over once, every call brings scalars only.  A basis keeps, in the memory of its
+// device, the tables {0 .. 8} P of its first min(n, MSM_BATCH_MAX) points (rows of up to MSM_BATCH_MAX terms run through k_msm_batch_sum /
+// _finish over them, whatever B is) and, when it has more points than that, the gathered-Niels records of all of them: one per point (mode 1:
+// jj_msm's plan without the copy and the conversion of the points) or one per point and window of its layout (mode 2: the window table of
+// jj_msm_kernels.h -- one bucket set, a record of one point, no Horner chain).  A prefix of m points takes the route m itself falls on.
+constexpr size_t MSM_BASIS_MAX = (size_t)1 << 24;            // points per basis: one Pippenger pass (and rows w * n + i below 2^31 for every layout)
+constexpr size_t MSM_BASIS_CHUNK = (size_t)1 << 16;          // points per launch of the table build (its workspace: 144 + 64 = 208 bytes per point and window)
+// auto never takes the window table: with jj_msm's window counts mode 2 was measured SLOWER than mode 1 at every size (profiles/msm_basis_ab.txt,
+// device-resident scalars: 2^14 terms 0.197 against 0.187 ms, 2^17 0.364 against 0.332 ms, 2^20 1.197 against 1.120 ms, spreads 0.001-0.005 ms: the
+// W-times larger gather costs more than the W - 1 bucket reduces and the Horner chain it removes).  Mode 2 stays an explicit opt-in (its
+// `windows` argument is there to look for a layout that wins); a table that would not fit half of the free memory is never auto's choice anyway.
+constexpr bool MSM_BASIS_AUTO_WINDOWS = false;
+struct jj_msm_basis {
+  int device = -1;
+  size_t n = 0, small_n = 0, bytes = 0;
+  int mode = 1, windows = SM_W, windows_arg = 0;
+  u32* small = nullptr;         // small_n tables of SM_SLOTS extended-Niels entries
+  u32* niels = nullptr;         // n > MSM_BATCH_MAX: n (mode 1) or windows x n (mode 2) records of GNIELS_WORDS words
+};
+static int msm_basis_plan(size_t n, int mode, int windows, uint64_t budget, int64_t out[4]) {
+  if (mode < 0 || mode > 2 || (windows != 0 && (windows < MSM_WINDOWS_MIN || windows > MSM_WINDOWS_MAX)) || n > MSM_BASIS_MAX) return JJ_ERR_INVALID;
+  const bool pip = n > MSM_BATCH_MAX;
+  const int W = pip ? (windows ? windows : msm_windows_default(n)) : SM_W;
+  const uint64_t small_bytes = (uint64_t)std::min(n, MSM_BATCH_MAX) * SM_SLOTS * ENIELS_WORDS * 4, row = (uint64_t)GNIELS_WORDS * 4;
+  const uint64_t b1 = small_bytes + (pip ? n * row : 0), b2 = small_bytes + (pip ? n * row * (uint64_t)W : 0);
+  int m = mode;
+  if (m == 0) m = MSM_BASIS_AUTO_WINDOWS && pip && b2 <= budget ? 2 : 1;
+  out[0] = m; out[1] = W; out[2] = (int64_t)(m == 2 ? b2 : b1); out[3] = pip ? 1 : 0;
+  return JJ_OK;
+}
+JJ_API int jj_plan_msm_basis(size_t n, int mode, int windows, uint64_t budget_bytes, int64_t out[4]) {
+  if (!out) return JJ_ERR_INVALID;
+  return msm_basis_plan(n, mode, windows, budget_bytes, out);
+}
+static void msm_basis_free(jj_msm_basis* b) {
+  if (b->small) (void)hipFree(b->small);
+  if (b->niels) (void)hipFree(b->niels);
+  delete b;
+}
+JJ_API int jj_msm_basis_create(jj_ctx* c, size_t n, const void* points, int mode, int windows, jj_msm_basis** out) {
+  if (!c || !out) return JJ_ERR_INVALID;
+  *out = nullptr;
+  int64_t plan[4];
+  if ((n && !points) || msm_basis_plan(n, mode, windows, 0, plan)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+  (void)msm_basis_plan(n, mode, windows, (uint64_t)free_b / 2, plan);
+  jj_msm_basis* b = new jj_msm_basis();
+  b->device = c->device; b->n = n; b->small_n = std::min(n, MSM_BATCH_MAX);
+  b->mode = (int)plan[0]; b->windows = (int)plan[1]; b->windows_arg = windows; b->bytes = (size_t)plan[2];
+  const bool pip = plan[3] != 0;
+  const size_t small_bytes = b->small_n * (size_t)(SM_SLOTS * ENIELS_WORDS) * 4, niels_bytes = b->bytes - small_bytes;
+  void *tmp = nullptr, *aff = nullptr;
+  auto fail = [&](int code, const char* what) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); if (tmp) (void)hipFree(tmp); if (aff) (void)hipFree(aff); msm_basis_free(b); c->err = what; return code; };
+  if (n == 0) { *out = b; return JJ_OK; }
+  if (hipMalloc((void**)&b->small, small_bytes) != hipSuccess || (pip && hipMalloc((void**)&b->niels, niels_bytes) != hipSuccess)) return fail(JJ_ERR_NOMEM, "jj_msm_basis_create: out of device memory for the tables");
+  int rc;
+  const void* dp;
+  if ((rc = stage_in(c, 1, points, 64 * n, &dp))) { const std::string keep = c->err; (void)fail(rc, ""); c->err = keep; return rc; }
+  hipLaunchKernelGGL(k_msm_batch_tables, dim3(blocks_for(4 * b->small_n)), dim3(256), 0, c->stream, b->small_n, dp, b->small);
+  if (pip) {
+    MsmParams mp;
+    msm_layout(mp, b->windows, 0, 1);
+    if (b->mode == 1) hipLaunchKernelGGL(k_msm_convert, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (const void*)nullptr, dp, mp, (u32*)nullptr, b->niels, 2);
+    else {
+      const size_t W = (size_t)b->windows, ch = std::min(n, MSM_BASIS_CHUNK);
+      if (hipMalloc(&tmp, ch * W * 4 * NL * 4) != hipSuccess || hipMalloc(&aff, ch * W * 64) != hipSuccess) return fail(JJ_ERR_NOMEM, "jj_msm_basis_create: out of device memory for the table build");
+      for (size_t lo = 0; lo < n; lo += ch) {
+        const size_t cn = std::min(ch, n - lo);
+        SoA park; park.base = (u32*)tmp; park.n = cn;
+        hipLaunchKernelGGL(k_msm_basis_chain, dim3(blocks_for(cn)), dim3(256), 0, c->stream, cn, (const void*)((const uint8_t*)dp + lo * 64), mp, park, aff);
+        for (size_t w = 0; w < W; w++)
+          hipLaunchKernelGGL(k_msm_convert, dim3(blocks_for(cn)), dim3(256), 0, c->stream, cn, (const void*)nullptr, (const void*)((const uint8_t*)aff + w * cn * 64), mp, (u32*)nullptr,
+                             b->niels + (w * n + lo) * (size_t)GNIELS_WORDS, 2);
+      }
+    }
+  }
+  // the caller's array (and the build's workspace) are free when the call returns
+  hipError_t e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return fail(JJ_ERR_HIP, "jj_msm_basis_create: the table build failed");
+  if (tmp) (void)hipFree(tmp);
+  if (aff) (void)hipFree(aff);
+  *out = b;
+  return JJ_OK;
+}
+JJ_API int jj_msm_basis_destroy(jj_ctx* c, jj_msm_basis* b) {
+  if (!c) return JJ_ERR_INVALID;
+  if (!b) return JJ_OK;
+  JJ_ENTER(c);
+  if (b->device != c->device) { c->err = "this MSM basis lives on another device"; return JJ_ERR_INVALID; }
+  msm_basis_free(b);
+  return JJ_OK;
+}
+JJ_API int jj_msm_basis_info(const jj_msm_basis* b, int64_t out[4]) {
+  if (!b || !out) return JJ_ERR_INVALID;
+  out[0] = (int64_t)b->n; out[1] = b->mode; out[2] = b->windows; out[3] = (int64_t)b->bytes;
+  return JJ_OK;
+}
+// one row over the basis's records (more than MSM_BATCH_MAX terms) or tables (a single short row): a job like jj_msm_begin's, finished by jj_msm_finish
+static int msm_basis_begin(jj_ctx* c, const jj_msm_basis* b, size_t m, const void* ds, bool spread, jj_msm_job** out) {
+  jj_msm_job* j;
+  int rc = msm_job_get(c, 1, &j); if (rc) return rc;
+  int k = 0;
+  if (spread && c->msm_lanes > 1) k = 1 + (int)(c->next_lane++ % (unsigned)c->msm_lanes);
+  MsmLane* L = nullptr;
+  if ((rc = msm_lane(c, k, &L))) { msm_job_put(c, j); return rc; }
+  const MsmTab tab{b->niels, b->mode == 2 ? b->n : (size_t)0, b->mode == 2 ? b->windows : b->windows_arg};
+  hipError_t e = hipSuccess;
+  if (m <= MSM_BATCH_MAX) {
+    // jj_msm's small-batch pass (msm_enqueue_small) without its table half
+    MsmParams mp;
+    msm_layout(mp, SM_W, 0, 1);
+    if (!(rc = ensure(c, L->buf[0], m * 32)) && !(rc = msm_ensure_ctl(c, *L))) {
+      u32* counters = (u32*)L->ctl.p; u32* part = (u32*)((uint8_t*)L->ctl.p + MSM_PART_OFF);
+      const u32 nblk = (u32)std::min<size_t>(c->msm_small_blk, std::max<size_t>(1, (m + 255) / 256));
+      hipLaunchKernelGGL(k_msm_small_recode, dim3(blocks_for(m)), dim3(256), 0, L->stream, m, ds, mp, (u32*)L->buf[0].p, counters);
+      hipLaunchKernelGGL(k_msm_small_sum, dim3(nblk, mp.Ws), dim3(4 * MSM_TREE_QUADS), 0, L->stream, m, mp, nblk, (const u32*)b->small, (const u32*)L->buf[0].p, part, counters, (u32*)j->host);
+    }
+  } else rc = msm_enqueue_pippenger(c, *L, m, ds, nullptr, 0, 1, j->host, &tab);
+  if (!rc) {
+    j->nrec = 1;
+    e = hipEventRecord(j->ev, L->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { c->err = std::string("MSM launch failed: ") + hipGetErrorString(e); rc = JJ_ERR_HIP; }
+  }
+  if (rc) { (void)hipStreamSynchronize(L->stream); (void)hipGetLastError(); msm_job_put(c, j); return rc; }
+  *out = j;
+  return JJ_OK;
+}
+JJ_API int jj_msm_basis_mul(jj_ctx* c, const jj_msm_basis* b, size_t B, size_t m, const void* scalars, void* out64) {
+  if (!c || !b) return JJ_ERR_INVALID;
+  if (B == 0) return JJ_OK;
+  if (B > SIZE_MAX / 64 || (m && (B > SIZE_MAX / m || B * m > SIZE_MAX / 32))) return JJ_ERR_INVALID;
+  if (!out64 || (m && !scalars) || m > b->n) return JJ_ERR_INVALID;
+  if (B == 1 && m) {
+    // one row: a job, queued under the context's lock and finished without it (as jj_msm: other threads may queue work while this one waits)
+    jj_msm_job* j = nullptr;
+    {
+      JJ_ENTER(c);
+      if (b->device != c->device) { c->err = "this MSM basis lives on another device"; return JJ_ERR_INVALID; }
+      const void* ds1;
+      int rc1;
+      if ((rc1 = stage_in(c, 0, scalars, 32 * m, &ds1)) || (rc1 = msm_basis_begin(c, b, m, ds1, false, &j))) return rc1;
+    }
+    return jj_msm_finish(j, out64);
+  }
+  JJ_ENTER(c);
+  if (b->device != c->device) { c->err = "this MSM basis lives on another device"; return JJ_ERR_INVALID; }
+  if (m == 0) {
+    if (is_device_ptr(out64)) {
+      HIPCHK(c, hipMemsetAsync(out64, 0, B * 64, c->stream));
+      HIPCHK(c, hipMemset2DAsync((uint8_t*)out64 + 32, 64, 1, 1, B, c->stream));
+      return finish(c, false);
+    }
+    for (size_t r = 0; r < B; r++) memcpy((uint8_t*)out64 + 64 * r, AFFINE_IDENTITY_BYTES, 64);
+    return JJ_OK;
+  }
+  int rc;
+  const void* ds;
+  if ((rc = stage_in(c, 0, scalars, 32 * B * m, &ds))) return rc;
+  if (m <= MSM_BATCH_MAX) {
+    OutRef o;
+    if ((rc = stage_out(c, c->out[0], out64, 64 * B, &o))) return rc;
+    if ((rc = msm_batch_enqueue(c, B, m, (const uint8_t*)ds, nullptr, true, (uint8_t*)o.dev, b->small))) return rc;
+    bool sync = false;
+    if ((rc = finish_out(c, o, &sync))) return rc;
+    return finish(c, sync);
+  }
+  // several long rows: one job per row, a few in flight over the context's lanes (as msm_batch_jobs)
+  std::vector<uint8_t> res(B * 64);
+  std::vector<jj_msm_job*> q;
+  const size_t depth = 2 * (size_t)std::max(1, c->msm_lanes);
+  size_t head = 0;
+  rc = JJ_OK;
+  auto finish_one = [&]() { const int r = jj_msm_finish(q[head], res.data() + 64 * head); head++; if (!rc) rc = r; };
+  for (size_t r = 0; r < B && !rc; r++) {
+    jj_msm_job* j = nullptr;
+    const int r1 = msm_basis_begin(c, b, m, (const uint8_t*)ds + r * m * 32, true, &j);
+    if (r1) { rc = r1; break; }
+    q.push_back(j);
+    if (q.size() - head > depth) finish_one();
+  }
+  while (head < q.size()) finish_one();
+  if (rc) return rc;
+  if (is_device_ptr(out64)) {
+    HIPCHK(c, hipMemcpyAsync(out64, res.data(), B * 64, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  } else memcpy(out64, res.data(), B * 64);
+  return JJ_OK;
 }
 // First half of an MSM that is cut across devices or ranks: the record of partial window sums, left where the
 // caller wants it (device memory: ready for an all_gather over RCCL; host memory: the call waits for the copy).

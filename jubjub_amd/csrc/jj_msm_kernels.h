@@ -508,13 +508,18 @@ __global__ void __launch_bounds__(1024) k_msm_plan(size_t n, u32 B, u32 ntiles, 
 // XCD-aware block mapping: workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  All tiles of one window
 // write into that window's 4-byte index segment, so a window is given to ONE XCD (slot = 8 * (j / ntiles) + xcd): the
 // partial-line writes of its tiles then meet in the same L2 and leave it as full lines.
-__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter(size_t n, size_t tile, u32 ntiles, MsmParams mp, const u32* kp, const u32* tbase, u32* idx) {
+// TAB (fixed-basis MSM over a window table, jj_msm_basis_*): the entry names row slot * tab_stride + term of the table instead of the term --
+// the accumulation kernels gather niels[entry] either way and stay as they are.  The two kernels below are the same body; jj_msm's has no
+// such argument.
+template <bool TAB>
+static JJ_DEV void msm_scatter_body(size_t n, size_t tile, u32 ntiles, const MsmParams& mp, const u32* kp, const u32* tbase, u32* idx, size_t tab_stride) {
   extern __shared__ u32 msm_lds[];
   const u32 xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
   const int s = (int)((j / ntiles) * 8 + xcd);
   const u32 tile_id = j % ntiles;
   if (s >= mp.Ws) return;
   const int w = msm_slot_window(mp, s);
+  const u32 row0 = TAB ? (u32)((size_t)s * tab_stride) : 0u;
   const u32* base = tbase + ((size_t)s * ntiles + tile_id) * mp.B;
   for (u32 b = threadIdx.x; b < mp.B; b += MSM_SORT_THREADS) msm_lds[b] = base[b];
   __syncthreads();
@@ -529,8 +534,14 @@ __global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter(size_t n, size
     }
     u32 slot[MSM_SORT_UNROLL];
     _Pragma("unroll") for (int q = 0; q < MSM_SORT_UNROLL; q++) slot[q] = a[q] ? atomicAdd(&msm_lds[a[q] - 1], 1u) : 0u;
-    _Pragma("unroll") for (int q = 0; q < MSM_SORT_UNROLL; q++) if (a[q]) idx[slot[q]] = (u32)(i0 + (size_t)q * MSM_SORT_THREADS) | (neg[q] << 31);
+    _Pragma("unroll") for (int q = 0; q < MSM_SORT_UNROLL; q++) if (a[q]) idx[slot[q]] = (row0 + (u32)(i0 + (size_t)q * MSM_SORT_THREADS)) | (neg[q] << 31);
   }
+}
+__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter(size_t n, size_t tile, u32 ntiles, MsmParams mp, const u32* kp, const u32* tbase, u32* idx) {
+  msm_scatter_body<false>(n, tile, ntiles, mp, kp, tbase, idx, 0);
+}
+__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter_tab(size_t n, size_t tile, u32 ntiles, MsmParams mp, const u32* kp, const u32* tbase, u32* idx, size_t tab_stride) {
+  msm_scatter_body<true>(n, tile, ntiles, mp, kp, tbase, idx, tab_stride);
 }
 // ---- One-pass sort in TWO launches (round 6; 2^14 .. 147 456 terms, windows of 11 bits).  Conversion, histogram, plan and scatter were four
 // launches of 6-30 us each, shorter than the host's launch interval: up to 35-40 us of the 2^17-term call were an idle GPU between them.
@@ -621,7 +632,8 @@ __global__ void __launch_bounds__(MSM_F2_THREADS) k_msm_front2(size_t n, const v
 // (Staging the part's entries through LDS and copying them out run by run, as k_msm_part_scatter does, was measured and dropped: 29-36 us
 // against 31 for the direct stores below -- with ~11 entries per run the copy-out saves few transactions and the block pays a second scan
 // and two more barriers.)
-__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter2(size_t n, u32 nparts, size_t part_terms, MsmParams mp, const void* scalars, const u32* tc, u32* off, u32* idx) {
+template <bool TAB>
+static JJ_DEV void msm_scatter2_body(size_t n, u32 nparts, size_t part_terms, const MsmParams& mp, const void* scalars, const u32* tc, u32* off, u32* idx, size_t tab_stride) {
   extern __shared__ u32 msm_lds[];
   __shared__ u32 part_s[17];
   const u32 xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
@@ -629,6 +641,7 @@ __global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter2(size_t n, u32
   const u32 part = j % nparts;
   if (s >= mp.Ws) return;
   const int w = msm_slot_window(mp, s);
+  const u32 row0 = TAB ? (u32)((size_t)s * tab_stride) : 0u;
   const u32 B = mp.B;
   const u32 bper = (B + 1023u) / 1024u, b0 = threadIdx.x * bper;             // consecutive buckets per thread (B <= 4096)
   const u32* rows = tc + (size_t)s * nparts * B;
@@ -661,8 +674,14 @@ __global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter2(size_t n, u32
     }
     u32 slot[MSM_SORT_UNROLL];
     _Pragma("unroll") for (int q = 0; q < MSM_SORT_UNROLL; q++) slot[q] = a[q] ? atomicAdd(&msm_lds[a[q] - 1], 1u) : 0u;
-    _Pragma("unroll") for (int q = 0; q < MSM_SORT_UNROLL; q++) if (a[q]) idx[slot[q]] = (u32)(i0 + (size_t)q * MSM_SORT_THREADS) | (neg[q] << 31);
+    _Pragma("unroll") for (int q = 0; q < MSM_SORT_UNROLL; q++) if (a[q]) idx[slot[q]] = (row0 + (u32)(i0 + (size_t)q * MSM_SORT_THREADS)) | (neg[q] << 31);
   }
+}
+__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter2(size_t n, u32 nparts, size_t part_terms, MsmParams mp, const void* scalars, const u32* tc, u32* off, u32* idx) {
+  msm_scatter2_body<false>(n, nparts, part_terms, mp, scalars, tc, off, idx, 0);
+}
+__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_scatter2_tab(size_t n, u32 nparts, size_t part_terms, MsmParams mp, const void* scalars, const u32* tc, u32* off, u32* idx, size_t tab_stride) {
+  msm_scatter2_body<true>(n, nparts, part_terms, mp, scalars, tc, off, idx, tab_stride);
 }
 // Two-pass sort for wide windows (>= 4096 buckets per window).  The single-pass scatter above ends in one 4-byte store per
 // entry into an index segment shared by all tiles of the window: every store opens its own cache line and most lines leave L2
@@ -735,7 +754,8 @@ constexpr int MSM_P1_PER = MSM_P1_TILE / MSM_SORT_THREADS;
 // tcs == nullptr (round 5, after k_msm_convert_hist): no per-tile offsets exist; the block forms the bins' first entries from the TOTALS per (slot, bin)
 // itself (a scan over at most 128 values) and reserves its run in every bin with one global atomic on the bin's cursor.  The order of the tiles' runs
 // inside a bin then depends on the order the blocks arrive in -- the entries of a bucket are added in another order, the sum is the same point.
-__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_part_scatter(size_t n, size_t tile, MsmParams mp, const u32* kp, const u32* tcs, u32* rec, uint8_t* lo8, const u32* totals, u32* cursor) {
+template <bool TAB>
+static JJ_DEV void msm_part_scatter_body(size_t n, size_t tile, const MsmParams& mp, const u32* kp, const u32* tcs, u32* rec, uint8_t* lo8, const u32* totals, u32* cursor, size_t tab_stride) {
   __shared__ u32 cnt[MSM_HB_MAX], live_s;
   __shared__ u32 st_rec[MSM_P1_TILE];
   __shared__ uint8_t st_lo[MSM_P1_TILE], st_bin[MSM_P1_TILE];
@@ -784,7 +804,7 @@ __global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_part_scatter(size_t n,
   __syncthreads();
   _Pragma("unroll") for (int q = 0; q < MSM_P1_PER; q++) if (a[q]) {
     const u32 bin = (a[q] - 1) >> MSM_LO_BITS, slot = loff[bin] + rank[q];
-    st_rec[slot] = (u32)(lo + tid + (size_t)q * MSM_SORT_THREADS) | (neg[q] << 31);
+    st_rec[slot] = ((TAB ? (u32)((size_t)blockIdx.y * tab_stride) : 0u) + (u32)(lo + tid + (size_t)q * MSM_SORT_THREADS)) | (neg[q] << 31);
     st_lo[slot] = (uint8_t)((a[q] - 1) & ((1u << MSM_LO_BITS) - 1u));
     st_bin[slot] = (uint8_t)bin;
   }
@@ -795,6 +815,12 @@ __global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_part_scatter(size_t n,
     rec[g] = st_rec[j];
     lo8[g] = st_lo[j];
   }
+}
+__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_part_scatter(size_t n, size_t tile, MsmParams mp, const u32* kp, const u32* tcs, u32* rec, uint8_t* lo8, const u32* totals, u32* cursor) {
+  msm_part_scatter_body<false>(n, tile, mp, kp, tcs, rec, lo8, totals, cursor, 0);
+}
+__global__ void __launch_bounds__(MSM_SORT_THREADS) k_msm_part_scatter_tab(size_t n, size_t tile, MsmParams mp, const u32* kp, const u32* tcs, u32* rec, uint8_t* lo8, const u32* totals, u32* cursor, size_t tab_stride) {
+  msm_part_scatter_body<true>(n, tile, mp, kp, tcs, rec, lo8, totals, cursor, tab_stride);
 }
 // SEGH: the block also does what k_seg_hist would do for its 256 buckets (it holds their counts anyway): the histogram of segment lengths of
 // tile s HB + coarse, key-major in bh, and the identity for empty buckets -- one launch and one pass over the offsets fewer (round 5).
@@ -1524,4 +1550,77 @@ __global__ void __launch_bounds__(64) k_msm_finish_dev(const u32* rec, void* out
     const Fe zi = Fq::invert(acc.z);
     store_affine(out64, 0, Fq::mul(acc.u, zi), Fq::mul(acc.v, zi));
   }
+}
+
+// ================================================================================================ fixed-basis MSM (jj_msm_basis_*)
+// The points of a basis are known before the first call, so what jj_msm rebuilds per call is built once: the {0 .. 8} P tables of the small
+// route (k_msm_batch_tables), the gathered-Niels records of the Pippenger route (k_msm_convert, what = 2) and, in mode 2, the WINDOW TABLE
+//     row (w, i) = 2^(start_w) P_i        (slot-major: entry w * n + i; a prefix of m <= n points is a shorter piece of every slot)
+// over the W windows of the basis's layout.  Digit d_w of k_i then selects row (w, i) and every window adds into ONE bucket set, because
+// k_i P_i = sum_w d_w (2^(start_w) P_i) holds in any abelian group: one reduce chain, a record of one point, no Horner chain.  The sort runs
+// as in jj_msm (same keys, same buckets per slot) with the k_msm_*_tab scatters above, the accumulation kernels are jj_msm's own, then
+// k_msm_fold_slots adds the W bucket sets into slot 0 and the reduce runs over a pass of one window (window 0: its 2^start is 1).
+//
+// k_msm_basis_chain: one lane per point walks P, 2^(s_1) P, ..., 2^(s_(W-1)) P (252 - width_(W-1) doublings), parks the W projective
+// points and the running products of their Z in `tmp` (SoA: coordinate 4 w + {0: U, 1: V, 2: Z, 3: Z_0 .. Z_w}), inverts the last product
+// and unwinds it (Montgomery's trick: one inversion and 3 (W - 1) products per point instead of W inversions) into canonical affine
+// points aff[w * n + i], which k_msm_convert turns into table rows slot by slot.
+__global__ void __launch_bounds__(256) k_msm_basis_chain(size_t n, const void* points, MsmParams mp, SoA tmp, void* aff) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Ext e = Curve::from_affine(load_affine(points, i));
+  Fe c = e.z;
+  #pragma unroll 1
+  for (int w = 0; w < mp.W; w++) {
+    if (w) {
+      const int d = msm_win_width(mp, w - 1);
+      #pragma unroll 1
+      for (int k = 0; k < d; k++) e = Curve::dbl(e);
+      c = Fq::mul(c, e.z);
+    }
+    tmp.put(4 * w, i, e.u); tmp.put(4 * w + 1, i, e.v); tmp.put(4 * w + 2, i, e.z); tmp.put(4 * w + 3, i, c);
+  }
+  Fe inv = Fq::invert(c);
+  #pragma unroll 1
+  for (int w = mp.W - 1; w >= 0; w--) {
+    const Fe u = tmp.get(4 * w, i), v = tmp.get(4 * w + 1, i);
+    Fe zi = inv;
+    if (w) { zi = Fq::mul(inv, tmp.get(4 * w - 1, i)); inv = Fq::mul(inv, tmp.get(4 * w + 2, i)); }
+    store_affine(aff, (size_t)w * n + i, Fq::mul(u, zi), Fq::mul(v, zi));
+  }
+}
+// a single short row over the basis's tables {0 .. 8} P: the scalar half of k_msm_small_tables, then k_msm_small_sum and jj_msm's host tail
+__global__ void __launch_bounds__(256) k_msm_small_recode(size_t n, const void* scalars, MsmParams mp, u32* kprime, u32* counters) {
+  if (blockIdx.x == 0 && threadIdx.x < MSM_COUNTER_WORDS) counters[threadIdx.x] = 0;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 k[8];
+  load8(k, scalars, i);
+  msm_recode(k, mp);
+  store8(kprime, i, k);
+}
+// buckets[0][b] <- sum over the slots s < Ws of buckets[s][b]: P lanes per bucket (a power of two <= 64, the host picks it so that the launch
+// fills the machine: with 1024 buckets one lane per bucket would be sixteen waves walking W - 1 additions each), lane p adds up slots p,
+// p + P, ... in whole-lane additions with the next bucket in flight (the loop of k_msm_fixup), then log2 P butterfly steps over the lanes fold
+// the partial sums and lane 0 stores.  Every bucket of every slot holds a point after the fix-up (the identity where it is empty, also above
+// the 2^(width - 1) buckets of a narrower window).  B P is a multiple of 64: whole waves, every lane takes part in the shuffles.
+__global__ void __launch_bounds__(256) k_msm_fold_slots(u32 B, u32 Ws, u32 P, ExtAoS buckets) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 b = (u32)(t / P), p = (u32)(t % P);
+  const bool live = b < B && p < Ws;
+  Ext acc = Curve::identity();
+  if (live) {
+    acc = aos_ext(buckets, (size_t)p * B + b);
+    u32 s = p + P;
+    Ext nx = aos_ext(buckets, (size_t)(s < Ws ? s : p) * B + b);
+    #pragma unroll 1
+    for (; s < Ws; s += P) {
+      const Ext cur = nx;
+      if (s + P < Ws) nx = aos_ext(buckets, (size_t)(s + P) * B + b);
+      acc = Curve::add(acc, Curve::to_niels(cur));
+    }
+  }
+  #pragma unroll 1
+  for (u32 d = P >> 1; d >= 1; d >>= 1) acc = Curve::add(acc, Curve::to_niels(wave_xor_partner(acc, (int)d)));
+  if (live && p == 0) aos_put_ext(buckets, b, acc);
 }

@@ -68,6 +68,20 @@ def _msm_batch_shapes(scalars, points):
     raise ValueError("points: shape (%d, 64) (shared) or (%d, %d, 64) expected, got %r" % (n, B, n, ps))
 
 
+_MSM_BASIS_MODES = {"auto": 0, "points": 1, "windows": 2, 0: 0, 1: 1, 2: 2}
+
+
+def _msm_basis_shapes(basis_n, scalars):
+    """(B, m, single) of jj_msm_basis_mul's scalars: (m, 32) -> one row, result (64,); (B, m, 32) -> result (B, 64); m <= the basis's points"""
+    ss = tuple(scalars.shape)
+    if len(ss) not in (2, 3) or ss[-1] != 32:
+        raise ValueError("scalars: shape (m, 32) or (B, m, 32) expected, got %r" % (ss,))
+    B, m = (1, ss[0]) if len(ss) == 2 else (ss[0], ss[1])
+    if m > basis_n:
+        raise ValueError("scalars: %d terms per row, the basis has %d points" % (m, basis_n))
+    return B, m, len(ss) == 2
+
+
 class _HostBlock:
     """owner of one jj_host_alloc block"""
 
@@ -92,6 +106,39 @@ class FixedBaseTable:
         if self._h is not None and self._engine._ctx is not None:
             self._engine._lib.jj_fixedbase_table_destroy(self._engine._ctx, self._h)
         self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MsmBasis:
+    """A fixed set of points resident on the device (Engine.msm_basis); Engine.msm_basis_mul sums scalar vectors against it."""
+
+    def __init__(self, engine, handle, n):
+        self._engine = engine
+        self._h = handle
+        self.n = n
+
+    @property
+    def info(self):
+        """{"n", "mode" ("points" | "windows"), "windows", "bytes"} of jj_msm_basis_info"""
+        out = (C.c_int64 * 4)()
+        self._engine._check(self._engine._lib.jj_msm_basis_info(self._h, out))
+        return {"n": out[0], "mode": "windows" if out[1] == 2 else "points", "windows": out[2], "bytes": out[3]}
+
+    def close(self):
+        if self._h is not None and self._engine._ctx is not None:
+            self._engine._lib.jj_msm_basis_destroy(self._engine._ctx, self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
@@ -458,6 +505,40 @@ class Engine:
             optr = oa.ptr
         self._bind_stream([a, p])
         self._check(self._lib.jj_msm_batch(self._ctx, C.c_size_t(B), C.c_size_t(n), a.ptr, p.ptr, C.c_int(shared), optr))
+        return out
+
+    def msm_basis(self, points, mode="auto", windows=0):
+        """Hands a fixed set of points over once (jj_msm_basis_create): points (n, 64), numpy or torch CUDA; the array may be reused
+        afterwards.  mode "auto" | "points" | "windows"; windows 0 or 16..36 (include/jubjub_hip.h)."""
+        ps = tuple(points.shape)
+        if len(ps) != 2 or ps[1] != 64:
+            raise ValueError("points: shape (n, 64) expected, got %r" % (ps,))
+        if mode not in _MSM_BASIS_MODES:
+            raise ValueError("mode: 'auto', 'points' or 'windows' expected, got %r" % (mode,))
+        if int(windows) != 0 and not 16 <= int(windows) <= 36:
+            raise ValueError("windows: 0 or 16..36 expected, got %r" % (windows,))
+        p = _Arg(points, 64)
+        self._bind_stream([p])
+        h = C.c_void_p()
+        self._check(self._lib.jj_msm_basis_create(self._ctx, C.c_size_t(p.n), p.ptr, C.c_int(_MSM_BASIS_MODES[mode]), C.c_int(int(windows)), C.byref(h)))
+        return MsmBasis(self, h, p.n)
+
+    def msm_basis_mul(self, basis, scalars, out=None):
+        """Sums of scalar vectors against the first m points of a basis (jj_msm_basis_mul): scalars (m, 32) -> (64,), (B, m, 32) -> (B, 64);
+        numpy arrays or torch CUDA tensors; `out`: a caller-owned array of that shape and of the scalars' kind."""
+        B, m, single = _msm_basis_shapes(basis.n, scalars)
+        a = _Arg(scalars, 32)
+        if out is None:
+            out, optr = self._alloc(a, B, 64)
+            if single:
+                out = out.reshape(64)
+        else:
+            oa = _Arg(out, 64)
+            if oa.n != B or oa.torch != a.torch or oa.keep is not out or tuple(out.shape) != ((64,) if single else (B, 64)):
+                raise ValueError("out: a contiguous uint8 array of shape %r of the scalars' kind expected" % (((64,) if single else (B, 64)),))
+            optr = oa.ptr
+        self._bind_stream([a])
+        self._check(self._lib.jj_msm_basis_mul(self._ctx, basis._h, C.c_size_t(B), C.c_size_t(m), a.ptr, optr))
         return out
 
     def msm_dev(self, scalars, points, out=None):

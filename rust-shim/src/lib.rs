@@ -239,6 +239,38 @@ impl<'a> FixedBase<'a> {
 }
 impl Drop for FixedBase<'_> { fn drop(&mut self) { unsafe { jj_fixedbase_table_destroy(self.gpu.0, self.t); } } }
 
+/// Many scalar vectors against ONE set of points (`jj_msm_basis_*`): the points go to the device once, every call brings scalars only.
+pub struct MsmBasis<'a> { gpu: &'a Gpu, b: *mut JjMsmBasis, n: usize }
+impl<'a> MsmBasis<'a> {
+    /// mode 0 = auto, 1 = points, 2 = windows; windows 0 = auto or 16..=36 (include/jubjub_hip.h)
+    pub fn new(gpu: &'a Gpu, points: &[AffinePoint], mode: c_int, windows: c_int) -> Self {
+        let (p, mut b) = (put_points(points), std::ptr::null_mut());
+        assert_eq!(unsafe { jj_msm_basis_create(gpu.0, points.len(), p.as_ptr() as _, mode, windows, &mut b) }, 0);
+        MsmBasis { gpu, b, n: points.len() }
+    }
+    pub fn len(&self) -> usize { self.n }
+    pub fn is_empty(&self) -> bool { self.n == 0 }
+    /// `sum_i points[i] * scalars[i]` over the first `scalars.len()` points of the basis
+    pub fn msm(&self, scalars: &[Fr]) -> ExtendedPoint {
+        assert!(scalars.len() <= self.n);
+        let s = put_scalars(scalars);
+        let mut out = [0u8; 64];
+        assert_eq!(unsafe { jj_msm_basis_mul(self.gpu.0, self.b, 1, scalars.len(), s.as_ptr() as _, out.as_mut_ptr() as _) }, 0);
+        get_point(&out).into()
+    }
+    /// one sum per row; every row has the same length `m <= len()`
+    pub fn msm_rows(&self, rows: &[Vec<Fr>]) -> Vec<ExtendedPoint> {
+        let m = rows.first().map_or(0, |r| r.len());
+        assert!(m <= self.n && rows.iter().all(|r| r.len() == m));
+        let flat: Vec<Fr> = rows.iter().flatten().copied().collect();
+        let s = put_scalars(&flat);
+        let mut out = vec![0u8; 64 * rows.len()];
+        assert_eq!(unsafe { jj_msm_basis_mul(self.gpu.0, self.b, rows.len(), m, s.as_ptr() as _, out.as_mut_ptr() as _) }, 0);
+        out.chunks_exact(64).map(|c| get_point(c).into()).collect()
+    }
+}
+impl Drop for MsmBasis<'_> { fn drop(&mut self) { unsafe { jj_msm_basis_destroy(self.gpu.0, self.b); } } }
+
 /// All GPUs of the node from one process: contiguous shards, one host thread and stream per device.
 pub struct Node(*mut JjMulti);
 impl Node {
