@@ -67,6 +67,7 @@ int jj_ctx_sync(jj_ctx* ctx);
  *   pipe_pageable_register 0|1 (0), pipe_copy_threads 0..64 (0 = auto), pipe_ramp 0|1 (1), pipe_prefault 0|1 (1), pipe_chunk_log2 0|8..24 (0 = per
  *                                 entry point): the host-buffer pipeline
  *   fixedbase_default 6|7 (7)     what window_bits = 0 means for jj_fixedbase_table_create
+ *   vb_mul2_window 4|5 (4)        jj_varbase_mul2_*: signed window width of the two-term ladder; the same results, 5 = twice the table workspace
  * Planner overrides, for tests and measurements (every value gives the same results): msm_windows, msm_small_max, msm_small_blk, msm_accum,
  * msm_seg_len, msm_chunk, msm_chunk_waves, msm_sort_blocks_per_cu, msm_reduce_chunk, msm_reduce_l1, msm_reduce_l2_chunk, msm_sort_hist_fused, msm_sort_two_pass,
  * msm_front1, msm_acc_lds, vb_ct_window, vb_quad_max, dec_c_mid (ranges: jj_pipeline.hip ctx_options; the parity rows of every one: tests/planner_matrix.py).
@@ -235,6 +236,29 @@ int jj_varbase_mul_vartime_compressed(jj_ctx*, size_t n, const void* scalars32, 
  * cf. WnafGroup src/lib.rs:1318-1336; the crate's Wnaf machinery is variable-time by design).  The kernel of jj_varbase_mul_vartime with the
  * one scalar read through a wave-uniform address. */
 int jj_varbase_mul_scalar(jj_ctx*, size_t n, const void* scalar32, const void* points64, void* out64);
+/* Two terms per unit, two variable bases: out[i] = to_affine(points_p[i] * a[i] + points_q[i] * b[i])   (the two-term linear combination of
+ * every verifier equation: Schnorr / RedJubjub checks, folding two generator vectors, re-randomised Pedersen openings).
+ * VARIABLE-TIME, for PUBLIC scalars, like jj_varbase_mul_vartime: ONE interleaved (Straus) ladder per unit -- both scalars in signed windows, the
+ * lane's two tables {0 .. 2^(w-1)} P and {0 .. 2^(w-1)} Q in device memory, read at digit-dependent addresses; per window two additions, then w
+ * doublings that serve both terms (w = 4, the default: 252 doublings + 128 additions against the 500 + 103 of two ladders and an addition).  Callers with
+ * secret scalars compose jj_varbase_mul and jj_point_add.
+ * Scalars are raw 32-byte patterns; only the low 252 bits are used (as jj_varbase_mul and jj_msm).  They are integers, never reduced mod r, so the
+ * result is exact on the whole curve: cofactor components, the identity, (0, -1), scalars >= r.  Results are specified for on-curve points.
+ * Every unit equals, byte for byte, jj_point_add(jj_varbase_mul(a, P), jj_varbase_mul(b, Q)) and row i of jj_msm_batch(n, 2, ...): canonical affine
+ * (u, v), or to_bytes of it for _compressed.  The Edwards law used is complete: Q = P, Q = -P, a P = -b Q, identity bases and zero scalars take no
+ * special path.
+ * Pointers may be host or device, mixed freely.  n = 0 succeeds and touches nothing.  JJ_ERR_INVALID before any device work: a NULL context, a
+ * NULL array with n > 0, NULL ab64.  Context lock, stream rules, jj_profile_*, the result pool and jj_host_alloc buffers: as jj_varbase_mul_vartime;
+ * all-host arrays of pipeline size go through the host-buffer pipeline in chunks.
+ * One unit per lane for every n: there is no quad-of-lanes form, so the latency of a small call is one lane's ladder.
+ * Option vb_mul2_window 4|5 (4): the signed window width; the same results for both.  4 = 2 x 9 table entries (2592 B of workspace per resident
+ * lane); 5 = 2 x 17 entries (4896 B) for 250 doublings + 102 additions: no faster beyond the spread at 2^20 units, 4.7 % slower at 2^16
+ * (profiles/varbase_mul2_ab.txt). */
+int jj_varbase_mul2_vartime(jj_ctx*, size_t n, const void* a32, const void* p64, const void* b32, const void* q64, void* out64);
+int jj_varbase_mul2_vartime_compressed(jj_ctx*, size_t n, const void* a32, const void* p64, const void* b32, const void* q64, void* out32);
+/* ONE pair of scalars for the whole batch (ab64 = a then b, 64 bytes, host or device): out[i] = a * P[i] + b * Q[i].  Both scalars are read through a
+ * wave-uniform address: recoding and digits are scalar-unit work. */
+int jj_varbase_mul2_scalars(jj_ctx*, size_t n, const void* ab64, const void* p64, const void* q64, void* out64);
 /* Same group element, but computed with the reference's exact 252-step double-and-add-always ladder and
  * returned in projective form: out = 160 bytes (U,V,Z,T1,T2 canonical LE) matching the Rust ExtendedPoint
  * fields bit for bit.  For parity testing, not for throughput. */

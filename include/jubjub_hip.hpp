@@ -448,6 +448,22 @@ inline AffineBatch multiply_vartime(const Context& c, const AffineBatch& points,
   c.check(jj_varbase_mul_vartime(c.raw(), points.len(), scalars.to_bytes().data(), points.coords().data(), out.data()));
   return AffineBatch(c, std::move(out));
 }
+// p[i] * a[i] + q[i] * b[i] in one interleaved ladder per unit (jj_varbase_mul2_vartime): variable-time, for PUBLIC scalars only; the same points as
+// multiply_vartime twice and a sum
+inline AffineBatch multiply2_vartime(const Context& c, const AffineBatch& p, const FrBatch& a, const AffineBatch& q, const FrBatch& b) {
+  if (p.len() != a.len() || q.len() != b.len() || p.len() != q.len()) throw Error(JJ_ERR_INVALID, "length mismatch");
+  std::vector<Bytes64> out(p.len());
+  c.check(jj_varbase_mul2_vartime(c.raw(), p.len(), a.to_bytes().data(), p.coords().data(), b.to_bytes().data(), q.coords().data(), out.data()));
+  return AffineBatch(c, std::move(out));
+}
+// p[i] * a + q[i] * b for one pair of scalars (jj_varbase_mul2_scalars)
+inline AffineBatch multiply2_scalars(const Context& c, const AffineBatch& p, const Bytes32& a, const AffineBatch& q, const Bytes32& b) {
+  if (p.len() != q.len()) throw Error(JJ_ERR_INVALID, "length mismatch");
+  Bytes32 ab[2] = {a, b};
+  std::vector<Bytes64> out(p.len());
+  c.check(jj_varbase_mul2_scalars(c.raw(), p.len(), ab, p.coords().data(), q.coords().data(), out.data()));
+  return AffineBatch(c, std::move(out));
+}
 // several fixed bases with short scalars through one LDS table set, one pass (sums of multiply_bits, lib.rs:297-301)
 class CompositeBase {
  public:

@@ -39,6 +39,9 @@ _SIGS.update({
     "jj_varbase_mul_vartime": [_sz, _vp, _vp, _vp],
     "jj_varbase_mul_vartime_compressed": [_sz, _vp, _vp, _vp],
     "jj_varbase_mul_scalar": [_sz, _vp, _vp, _vp],
+    "jj_varbase_mul2_vartime": [_sz, _vp, _vp, _vp, _vp, _vp],
+    "jj_varbase_mul2_vartime_compressed": [_sz, _vp, _vp, _vp, _vp, _vp],
+    "jj_varbase_mul2_scalars": [_sz, _vp, _vp, _vp, _vp],
     "jj_varbase_mul_compressed": [_sz, _vp, _vp, _vp],
     "jj_fixedbase_mul_compressed": [_vp, _sz, _vp, _vp],
     "jj_fixedbase_table_destroy": [_vp],

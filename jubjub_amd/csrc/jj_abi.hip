@@ -245,6 +245,99 @@ JJ_API int jj_varbase_mul_scalar(jj_ctx* c, size_t n, const void* scalar32, cons
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
 }
+// ---- two terms per unit: out[i] = a[i] P[i] + b[i] Q[i] in one interleaved ladder (k_varbase_mul2, jj_straus.h).  VARIABLE-TIME like the
+// _vartime entry points above (per-lane tables in memory, digit-dependent addresses).  The lane kernel serves every n (no quad form).
+// shared: `da` is ONE pair of scalars (a then b, 64 device bytes) for the whole batch, db is unused.
+static int varbase_mul2_to_ext(jj_ctx* c, size_t n, const void* da, const void* dp, const void* db, const void* dq, SoA ext, bool shared) {
+  unsigned blocks; size_t threads;
+  varbase_geometry(c, n, &blocks, &threads);
+  const bool w5 = c->vb_mul2_window == 5;
+  int rc = ensure(c, c->ws->tables, threads * (size_t)(w5 ? Straus<5>::LANE_WORDS : Straus<4>::LANE_WORDS) * 4); if (rc) return rc;
+  if ((rc = ensure(c, c->ws->cursor, 64))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->ws->cursor.p, 0, 8, c->stream));          // the waves' work cursor
+  u32* tables = (u32*)c->ws->tables.p; unsigned long long* cursor = (unsigned long long*)c->ws->cursor.p;
+  if (w5 && shared) hipLaunchKernelGGL((k_varbase_mul2<5, true>), dim3(blocks), dim3(256), 0, c->stream, n, da, dp, db, dq, tables, ext, cursor);
+  else if (w5) hipLaunchKernelGGL((k_varbase_mul2<5, false>), dim3(blocks), dim3(256), 0, c->stream, n, da, dp, db, dq, tables, ext, cursor);
+  else if (shared) hipLaunchKernelGGL((k_varbase_mul2<4, true>), dim3(blocks), dim3(256), 0, c->stream, n, da, dp, db, dq, tables, ext, cursor);
+  else hipLaunchKernelGGL((k_varbase_mul2<4, false>), dim3(blocks), dim3(256), 0, c->stream, n, da, dp, db, dq, tables, ext, cursor);
+  return JJ_OK;
+}
+static int varbase_mul2_api(jj_ctx* c, size_t n, const void* a, const void* p, const void* b, const void* q, void* out, int mode) {
+  if (!c) return JJ_ERR_INVALID;
+  if (n && (!a || !p || !b || !q || !out)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (const size_t ch = pipe_chunk_for(c, n, 18); ch && all_host({a, p, b, q, out})) {
+    const HostIn in[4] = {{a, 32}, {p, 64}, {b, 32}, {q, 64}};
+    const HostOut ho[1] = {{out, (size_t)(mode ? 32 : 64)}};
+    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
+      int rc2;
+      if ((rc2 = ensure_ext(c, cn, 3))) return rc2;
+      SoA ext = soa_of(c->ws->ext, cn);
+      if ((rc2 = varbase_mul2_to_ext(c, cn, di[0], di[1], di[2], di[3], ext, false))) return rc2;
+      if ((rc2 = pipe_to_tail(c))) return rc2;
+      return normalize_launch(c, cn, ext, dout[0], mode);
+    });
+    if (prc <= 0) return prc;      // +1: buffers could not be page-locked -> plain staging below
+  }
+  const void *da, *dp, *db, *dq; int rc; OutRef o;
+  if ((rc = stage_in(c, 0, a, 32 * n, &da))) return rc;
+  if ((rc = stage_in(c, 1, p, 64 * n, &dp))) return rc;
+  if ((rc = stage_in(c, 2, b, 32 * n, &db))) return rc;
+  if ((rc = stage_in(c, 3, q, 64 * n, &dq))) return rc;
+  if ((rc = stage_out(c, c->out[0], out, (mode ? 32 : 64) * n, &o))) return rc;
+  if ((rc = ensure_ext(c, n, 3))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  if (n) {
+    prof_mark(c, 0);
+    if ((rc = varbase_mul2_to_ext(c, n, da, dp, db, dq, ext, false))) return rc;
+    prof_mark(c, 1);
+    if ((rc = normalize_launch(c, n, ext, o.dev, mode))) return rc;
+    prof_mark(c, 2);
+  }
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
+JJ_API int jj_varbase_mul2_vartime(jj_ctx* c, size_t n, const void* a32, const void* p64, const void* b32, const void* q64, void* out64) { return varbase_mul2_api(c, n, a32, p64, b32, q64, out64, 0); }
+JJ_API int jj_varbase_mul2_vartime_compressed(jj_ctx* c, size_t n, const void* a32, const void* p64, const void* b32, const void* q64, void* out32) { return varbase_mul2_api(c, n, a32, p64, b32, q64, out32, 1); }
+// one pair of scalars, many pairs of bases: both scalars are read through a wave-uniform address (k_varbase_mul2<.., SHARED>)
+JJ_API int jj_varbase_mul2_scalars(jj_ctx* c, size_t n, const void* ab64, const void* p, const void* q, void* out) {
+  if (!c || !ab64) return JJ_ERR_INVALID;
+  if (n && (!p || !q || !out)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (!n) return JJ_OK;
+  int rc;
+  if ((rc = ensure(c, c->ws_tmp[1], 64))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->ws_tmp[1].p, ab64, 64, is_device_ptr(ab64) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  const void* dab = c->ws_tmp[1].p;
+  if (const size_t ch = pipe_chunk_for(c, n, 18); ch && all_host({p, q, out})) {
+    const HostIn in[2] = {{p, 64}, {q, 64}};
+    const HostOut ho[1] = {{out, 64}};
+    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
+      int rc2;
+      if ((rc2 = ensure_ext(c, cn, 3))) return rc2;
+      SoA ext = soa_of(c->ws->ext, cn);
+      if ((rc2 = varbase_mul2_to_ext(c, cn, dab, di[0], nullptr, di[1], ext, true))) return rc2;
+      if ((rc2 = pipe_to_tail(c))) return rc2;
+      return normalize_launch(c, cn, ext, dout[0], 0);
+    });
+    if (prc <= 0) return prc;
+  }
+  const void *dp, *dq; OutRef o;
+  if ((rc = stage_in(c, 1, p, 64 * n, &dp))) return rc;
+  if ((rc = stage_in(c, 3, q, 64 * n, &dq))) return rc;
+  if ((rc = stage_out(c, c->out[0], out, 64 * n, &o))) return rc;
+  if ((rc = ensure_ext(c, n, 3))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  prof_mark(c, 0);
+  if ((rc = varbase_mul2_to_ext(c, n, dab, dp, nullptr, dq, ext, true))) return rc;
+  prof_mark(c, 1);
+  if ((rc = normalize_launch(c, n, ext, o.dev, 0))) return rc;
+  prof_mark(c, 2);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
 JJ_API int jj_varbase_mul_exact(jj_ctx* c, size_t n, const void* scalars, const void* points, void* out160) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);

@@ -213,6 +213,8 @@ struct jj_ctx {
   int vb_ct_window = 0;          // constant-time ladder: 0 = the x-only Montgomery ladder (k_varbase_mont, the default; not settable), or the Edwards
                                  // ladder with signed windows of 3 (k_varbase_ct3) or 2 (k_varbase_ct) bits for A/B runs; JJ_VB_CT_WINDOW
   int vb_quad_max = 32768;       // batches up to this size run one scalar-mul per quad of lanes (JJ_VB_QUAD_MAX; 0 = never)
+  int vb_mul2_window = 4;        // two-term ladder (k_varbase_mul2): signed window width, 4 or 5 (option vb_mul2_window; the same results).  4: as fast as 5 within the spread at 2^20 units, 4.7 % faster at 2^16,
+                                 // and half the table workspace per lane (profiles/varbase_mul2_ab.txt)
   int fb_gather_blocks_per_cu = 3;   // wide-window fixed-base kernel: resident blocks of 256 per CU (JJ_FB_GATHER_BLOCKS_PER_CU)
   int vb_blocks_per_cu = 2;      // var-base ladder: resident blocks of 256 per CU (the ladder holds ~190 VGPRs: 2 waves per SIMD); JJ_VB_BLOCKS_PER_CU
   // multi-rank MSM exchange (jj_ctx_set_comm / jj_msm_allgather): the caller's RCCL communicator, ncclAllGather of the library that made it

@@ -468,6 +468,31 @@ __global__ void __launch_bounds__(256, JJ_VB_MINWAVES) k_varbase(size_t n, const
   }
 }
 #endif  // JJ_KERNELS_BATCH
+// Two terms per unit, a P + b Q, in one interleaved ladder (jj_straus.h): k_varbase's persistent grid and cursor, a lane slot of two tables.
+// W: signed window width (5 or 4).  SHARED: `a` holds ONE pair of scalars for the whole batch (a then b, 64 bytes), read through a
+// wave-uniform address: both recodings and every digit are scalar-unit work.
+}  // namespace jj
+#include "jj_straus.h"
+namespace jj {
+#ifdef JJ_KERNELS_BATCH
+template <int W, bool SHARED>
+__global__ void __launch_bounds__(256, 2) k_varbase_mul2(size_t n, const void* a, const void* p, const void* b, const void* q, u32* tables, SoA ext, unsigned long long* cursor) {
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u32* slot = tables + gtid * (size_t)Straus<W>::LANE_WORDS;
+  size_t i;
+  #pragma unroll 1
+  while (next_wave_units(cursor, n, i)) {
+    if (i < n) {                                           // ragged last wave: as k_varbase
+      u32 ka[8], kb[8];
+      load8(ka, a, SHARED ? (size_t)0 : i);
+      load8(kb, SHARED ? a : b, SHARED ? (size_t)1 : i);
+      const Affine P = load_affine(p, i), Q = load_affine(q, i);
+      const Ext r = Straus<W>::mul2(P, Q, ka, kb, slot);
+      ext.put(0, i, r.u); ext.put(1, i, r.v); ext.put(2, i, r.z);
+    }
+  }
+}
+#endif  // JJ_KERNELS_BATCH
 // the reference's exact ladder; writes all five projective coordinates canonically (160 B)
 #ifdef JJ_KERNELS_BATCH
 __global__ void __launch_bounds__(256) k_varbase_exact(size_t n, const void* scalars, const void* points, void* out160) {

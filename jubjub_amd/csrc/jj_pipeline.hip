@@ -400,6 +400,7 @@ static const CtxOption* ctx_options() {
     JJ_OPT("pipe_prefault", 0, 1, pipe_prefault, bool),
     {"pipe_chunk_log2", 0, 24, [](jj_ctx* c, long long v) { c->pipe_chunk = v >= 8 ? (size_t)1 << v : 0; }, [](const jj_ctx* c) { long long l = 0; while (((size_t)1 << l) < c->pipe_chunk) l++; return c->pipe_chunk ? l : 0LL; }},
     {"fixedbase_default", 6, 7, [](jj_ctx* c, long long v) { c->fb_default_kind = (int)v; }, [](const jj_ctx* c) { return (long long)c->fb_default_kind; }},
+    JJ_OPT("vb_mul2_window", 4, 5, vb_mul2_window, int),                     // jj_varbase_mul2_*: signed window width; the same results, 4 = half the table workspace (2592 B per lane)
     // planner overrides (tests and measurements; every value gives the same results)
     JJ_OPT("msm_windows", 0, MSM_WINDOWS_MAX, msm_windows, int),             // 0 = from n; else 16..36
     JJ_OPT("msm_small_max", 0, 1 << 20, msm_small_max, int),

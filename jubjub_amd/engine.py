@@ -427,6 +427,26 @@ class Engine:
         self._check(self._lib.jj_varbase_mul_scalar(self._ctx, C.c_size_t(p.n), a.ptr, p.ptr, optr))
         return out
 
+    def varbase_mul2_vartime(self, a, p, b, q, out=None):
+        """p[i] * a[i] + q[i] * b[i] for PUBLIC scalars in one interleaved ladder per unit (jj_varbase_mul2_vartime): byte for byte
+        point_add(varbase_mul(a, p), varbase_mul(b, q)); two per-lane window tables in memory, digit-dependent addresses"""
+        return self._call("jj_varbase_mul2_vartime", [a, p, b, q], [32, 64, 32, 64], [64], out=out)
+
+    def varbase_mul2_vartime_compressed(self, a, p, b, q, out=None):
+        return self._call("jj_varbase_mul2_vartime_compressed", [a, p, b, q], [32, 64, 32, 64], [32], out=out)
+
+    def varbase_mul2_scalars(self, ab, p, q):
+        """p[i] * a + q[i] * b for ONE pair of 32-byte scalars (ab = a then b: 64 bytes or 2 x 32, numpy or torch), every pair of points of the batch."""
+        s, pp, qq = _Arg(ab, 64), _Arg(p, 64), _Arg(q, 64)
+        if s.n != 1:
+            raise ValueError("ab must be 64 bytes: a then b")
+        if pp.n != qq.n:
+            raise ValueError("length mismatch: %d vs %d" % (pp.n, qq.n))
+        self._bind_stream([s, pp, qq])
+        out, optr = self._alloc(pp, pp.n, 64)
+        self._check(self._lib.jj_varbase_mul2_scalars(self._ctx, C.c_size_t(pp.n), s.ptr, pp.ptr, qq.ptr, optr))
+        return out
+
     def varbase_mul_compressed(self, scalars, points, out=None):
         return self._call("jj_varbase_mul_compressed", [scalars, points], [32, 64], [32], out=out)
 

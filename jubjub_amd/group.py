@@ -188,6 +188,15 @@ class Points:
     def __mul__(self, k):                                   # `&ExtendedPoint * &Fr` src/lib.rs:873-879
         return self.multiply_bits(k.to_bytes())
 
+    def mul2_vartime(self, k, other, l):
+        """self * k + other * l, unit by unit, for PUBLIC scalars k, l (Fr batches or raw 32-byte rows): one interleaved ladder per unit
+        (Engine.varbase_mul2_vartime) instead of two products (src/lib.rs:873-879) and a sum (1012-1019); the same points"""
+        kb = _as_rows(k.to_bytes() if hasattr(k, "to_bytes") else k, 32)
+        lb = _as_rows(l.to_bytes() if hasattr(l, "to_bytes") else l, 32)
+        if not (kb.shape[0] == lb.shape[0] == len(self) == len(other)):
+            raise ValueError("length mismatch")
+        return Points(self.engine, self.engine.varbase_mul2_vartime(kb, self.data, lb, other.data))
+
     def sum(self):                                          # Sum (src/lib.rs:183-193)
         return Points(self.engine, self.engine.point_sum(self.data))
 

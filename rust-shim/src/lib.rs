@@ -204,6 +204,16 @@ impl Gpu {
         (0..n).map(|i| get_point(&out[64 * i..64 * i + 64])).collect()
     }
 
+    /// `p[i] * a[i] + q[i] * b[i]` for PUBLIC scalars (the two-term combination of a verifier equation) in one interleaved ladder per unit
+    /// (`jj_varbase_mul2_vartime`): the same points as `multiply_batch_vartime` twice and a sum, variable-time like it.
+    pub fn multiply2_batch_vartime(&self, a: &[Fr], p: &[AffinePoint], b: &[Fr], q: &[AffinePoint]) -> Vec<AffinePoint> {
+        assert!(a.len() == p.len() && b.len() == q.len() && a.len() == b.len());
+        let (n, sa, pp, sb, pq) = (a.len(), put_scalars(a), put_points(p), put_scalars(b), put_points(q));
+        let mut out = vec![0u8; 64 * n];
+        assert_eq!(unsafe { jj_varbase_mul2_vartime(self.0, n, sa.as_ptr() as _, pp.as_ptr() as _, sb.as_ptr() as _, pq.as_ptr() as _, out.as_mut_ptr() as _) }, 0);
+        out.chunks_exact(64).map(get_point).collect()
+    }
+
     /// `is_torsion_free` (src/lib.rs:709-711) for a whole vector.
     pub fn is_torsion_free_batch(&self, points: &[AffinePoint]) -> Vec<bool> {
         let (n, p) = (points.len(), put_points(points));
