@@ -429,7 +429,9 @@ int jj_msm_allgather_begin(jj_ctx*, size_t n, const void* scalars32, const void*
 int jj_decompress(jj_ctx*, size_t n, const void* in32, unsigned flags, void* out64, uint8_t* ok);
 /* AffinePoint::to_bytes src/lib.rs:455-464 */
 int jj_compress(jj_ctx*, size_t n, const void* points64, void* out32);
-/* batch_normalize src/lib.rs:1084-1107: n x 160 bytes (U,V,Z,T1,T2 canonical LE) -> n x 64 bytes affine */
+/* batch_normalize src/lib.rs:1084-1107: n x 160 bytes (U,V,Z,T1,T2 canonical LE) -> n x 64 bytes affine.  A row with Z = 0 (mod q)
+ * yields (0, 0) and leaves the other rows alone, as ff's BatchInverter does; coordinates of q or more are reduced mod q, as in the
+ * field entry points; T1 and T2 are not read. */
 int jj_batch_normalize(jj_ctx*, size_t n, const void* ext160, void* out64);
 
 
