@@ -448,12 +448,13 @@ def test_msm_around_the_large_input_switch(eng):
         assert (eng.msm(S, P) == O.msm(S, P)).all(), n
 
 
-def test_msm_big_bucket_list_overflow(eng):
+def test_msm_many_buckets_through_the_wave_wide_fixup(eng):
     """128 distinct scalars repeated over 2^17 terms: every non-empty bucket holds 1024 entries, i.e. more chunk heads than the
     FIXUP_SERIAL_MAX (32) a pair of lanes of k_msm_fixup walks itself, and there are about 128 x 23 such buckets.  The chunked path
     folds every one of them inside k_msm_fixup: the whole wave takes a big bucket after the pairs' own buckets (64 lanes over the heads,
-    a butterfly over the lanes), in the same launch.  Nothing here can overflow: the chunked path keeps no list of big buckets (the
-    test's name is older than that); k_msm_fixup_big serves the segment path alone."""
+    a butterfly over the lanes), in the same launch.  The chunked path keeps no list of big buckets, so nothing here can overflow; the
+    list of the segment path (k_msm_fixup_big) is filled beyond its capacity by the big-list-overflow layout of
+    tests/test_gpu_msm_buckets.py."""
     n = 1 << 17
     base = rand_scalars(71, 128, full_width=True)
     S = np.ascontiguousarray(base[np.arange(n) % 128])
