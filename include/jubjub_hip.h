@@ -68,6 +68,8 @@ int jj_ctx_sync(jj_ctx* ctx);
  *                                 entry point): the host-buffer pipeline
  *   fixedbase_default 6|7 (7)     what window_bits = 0 means for jj_fixedbase_table_create
  *   vb_mul2_window 4|5 (4)        jj_varbase_mul2_*: signed window width of the two-term ladder; the same results, 5 = twice the table workspace
+ *   msm_ragged_slice_min 1..8192 (16), msm_ragged_waves 1..65536 (2048), msm_ragged_round_terms 1..2^18 (2^18): jj_msm_ragged's planner -- terms
+ *                                 per slice at least, waves the short segments are cut for, terms per round of tables; the same results for every value
  * Planner overrides, for tests and measurements (every value gives the same results): msm_windows, msm_small_max, msm_small_blk, msm_accum,
  * msm_seg_len, msm_chunk, msm_chunk_waves, msm_sort_blocks_per_cu, msm_reduce_chunk, msm_reduce_l1, msm_reduce_l2_chunk, msm_sort_hist_fused, msm_sort_two_pass,
  * msm_front1, msm_acc_lds, vb_ct_window, vb_quad_max, dec_c_mid (ranges: jj_pipeline.hip ctx_options; the parity rows of every one: tests/planner_matrix.py).
@@ -338,6 +340,41 @@ int jj_msm_dev(jj_ctx*, size_t n, const void* scalars32, const void* points64, v
  * run in rounds of whole rows.  n > 8192: every row is a jj_msm_begin job (device-pointer rows alternate over the context's
  * MSM lanes) finished by the host tail, and the call returns only after every row is finished, whatever the pointers. */
 int jj_msm_batch(jj_ctx*, size_t B, size_t n, const void* scalars32, const void* points64, int points_shared, void* out64);
+/* S independent MSMs of DIFFERENT lengths: sums over consecutive runs of ONE term array (CSR layout):
+ *   out64[s] = to_affine(sum_{offsets[s] <= i < offsets[s+1]} points[i] * scalars[i])   for s < S
+ * Every segment equals jj_msm(ctx, len, its scalars, its points) byte for byte (raw 32-byte scalars, low 252 bits used; exact on the whole
+ * curve: cofactor components, the identity, (0, -1), scalars >= r).  VARIABLE-TIME, like jj_msm.
+ *   offsets    S + 1 values in HOST memory, offsets[0] = 0, non-decreasing; N = offsets[S] terms in all.  Read before the call returns.
+ *   scalars32  N x 32 bytes, points64 N x 64 bytes (host or device, mixed freely); out64 S x 64 bytes (host or device)
+ * An empty segment writes the identity (0, 1).  S = 0 succeeds and touches nothing; N = 0 with S > 0 writes S identities (scalars32 and
+ * points64 may then be NULL).
+ * JJ_ERR_INVALID, before any device work: a NULL context; NULL offsets or out64 with S > 0; NULL scalars32 or points64 with N > 0;
+ * offsets[0] != 0; a decreasing pair; offsets in device memory; S * 64 or N * 64 beyond size_t.
+ * Segments of at most 8192 terms (MSM_BATCH_MAX), the short ones, run in a few launches on the context's stream: per-term tables {0..8}P as
+ * in jj_msm_batch, a work list of slices built on the host (one wave per slice, one lane per window; the last slice of a segment to finish
+ * adds the others), a device-side Horner chain and inversion per segment.  Tables are built for at most 2^18 terms at a time (340 MB of device
+ * workspace): more terms run in rounds of whole segments.  Longer segments are one jj_msm_begin job each (over the context's MSM lanes),
+ * finished by the host tail.  With only short segments and only device pointers the call queues work and returns; with any long segment or
+ * any host pointer it returns with the results in place.  Arrays are staged whole: there is no host-buffer pipeline.
+ * jj_plan_msm_ragged / jj_plan_msm_ragged_items: what the call does with these offsets -- pure functions (no context, no device), the same code
+ * as the call's own planner.  slice_min / waves / round_terms: 0 = the defaults 16 / 2048 / 2^18 (a context: options msm_ragged_slice_min,
+ * msm_ragged_waves, msm_ragged_round_terms).  Slice length t = max(slice_min, ceil(N_short / waves)) with N_short the terms of the short
+ * segments; a short segment of len terms is cut into ceil(len / t) slices of near-equal length (each 1 .. t terms); a round holds whole short
+ * segments, consecutive in input order, of at most round_terms terms together (a segment above round_terms: a round of its own); a long segment
+ * belongs to no round and closes the round before it, so that a round's terms are one contiguous range.
+ *   out[0] = short non-empty segments, out[1] = long segments (jobs route), out[2] = work items (slices), out[3] = rounds
+ *   items: 4 values per work item -- round, segment, first term, end term -- in launch order; at most cap items are written, *count is always
+ *   set (items = NULL with cap = 0: the count only); JJ_ERR_INVALID if cap is too small, and for offsets jj_msm_ragged refuses.
+ * Measured (profiles/msm_ragged_ab.txt; one MI355X, 2^18 terms, device-resident, median ms per call [min .. max] of five alternating rounds):
+ *   1024 segments of 256 terms             ragged 2.1396 [2.1286 .. 2.2154]   jj_msm_batch on the same rectangle 2.0663 [2.0570 .. 2.0811] and
+ *                                          2.1553 [2.1526 .. 2.1710] (the same call in two slots of the loop)   a jj_msm_begin job per segment 45.9
+ *   geometric lengths, mean 64             ragged 2.3974 [2.3657 .. 2.4781]   zero-padded jj_msm_batch 11.8380 (4.94 x)   jobs 186.95 (78 x)
+ *   90 % of 4 terms, 10 % of 2000          ragged 2.2651 [2.2604 .. 2.2786]   zero-padded jj_msm_batch 15.1859 (6.70 x)   jobs 54.07 (24 x)
+ * On a true rectangle the call sits within the spread of jj_msm_batch (its sum kernel is 2-4 % slower in a kernel trace,
+ * profiles/msm_ragged_kernels.txt); on skewed lengths it beats both the padded batch and the job per segment. */
+int jj_msm_ragged(jj_ctx*, size_t S, const uint64_t* offsets, const void* scalars32, const void* points64, void* out64);
+int jj_plan_msm_ragged(size_t S, const uint64_t* offsets, int slice_min, int waves, uint64_t round_terms, int64_t out[4]);
+int jj_plan_msm_ragged_items(size_t S, const uint64_t* offsets, int slice_min, int waves, uint64_t round_terms, uint64_t* items, size_t cap, size_t* count);
 /* Fixed-basis MSM: many scalar vectors against ONE set of points that is handed over once (Pedersen vector commitments, value / note
  * commitments over many generators, an IPA prover, a batch verifier with a fixed key set) -- the MSM's counterpart of
  * jj_fixedbase_table_create / jj_fixedbase_mul.  jj_msm_basis_create copies the n points (host or device pointer; the caller's array may be

@@ -319,6 +319,16 @@ inline AffineBatch msm_batch(const Context& c, const std::vector<AffineBatch>& p
   c.check(jj_msm_batch(c.raw(), points.size(), n, fs.data(), fp.data(), 0, out.data()));
   return AffineBatch(c, std::move(out));
 }
+// Sums of DIFFERENT lengths in one call (jj_msm_ragged): row s = sum of points[i] * scalars[i] over offsets[s] <= i < offsets[s + 1];
+// offsets: S + 1 values, offsets[0] = 0, non-decreasing, offsets[S] = points.len().  An empty run gives the identity; no offsets: no rows.
+inline AffineBatch msm_ragged(const Context& c, const AffineBatch& points, const FrBatch& scalars, const std::vector<uint64_t>& offsets) {
+  if (points.len() != scalars.len()) throw Error(JJ_ERR_INVALID, "length mismatch");
+  if (!offsets.empty() && offsets.back() != points.len()) throw Error(JJ_ERR_INVALID, "the last offset must be the number of terms");
+  const size_t S = offsets.empty() ? 0 : offsets.size() - 1;
+  std::vector<Bytes64> out(S);
+  c.check(jj_msm_ragged(c.raw(), S, offsets.data(), scalars.to_bytes().data(), points.coords().data(), out.data()));
+  return AffineBatch(c, std::move(out));
+}
 
 // Many scalar vectors against ONE set of points (jj_msm_basis_*): the points go to the device once (tables owned by this object), every
 // msm(basis, rows) brings scalars only.  Mode: 0 = auto, 1 = points, 2 = windows; windows: 0 = auto or 16 .. 36 (jubjub_hip.h).

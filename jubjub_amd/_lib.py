@@ -58,6 +58,7 @@ _SIGS.update({
     "jj_msm_allgather": [_sz, _vp, _vp, C.c_int, _vp],
     "jj_msm_allgather_begin": [_sz, _vp, _vp, C.c_int, C.POINTER(_vp)],
     "jj_msm_batch": [_sz, _sz, _vp, _vp, C.c_int, _vp],
+    "jj_msm_ragged": [_sz, _vp, _vp, _vp, _vp],
     "jj_msm_basis_create": [_sz, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
     "jj_msm_basis_destroy": [_vp],
     "jj_msm_basis_mul": [_vp, _sz, _sz, _vp, _vp],
@@ -93,7 +94,8 @@ EXPORTS = sorted(list(_SIGS) + ["jj_ctx_create", "jj_ctx_destroy", "jj_last_erro
                                 "jj_msm_fold_partials", "jj_msm_finish", "jj_msm_combine",
                                 "jj_host_alloc", "jj_host_free", "jj_host_register", "jj_host_unregister",
                                 "jj_result_acquire", "jj_result_release", "jj_result_pool_stats",
-                                "jj_plan_host_chunks", "jj_plan_msm_host_passes", "jj_msm_basis_info", "jj_plan_msm_basis", "jj_ctx_set_option", "jj_ctx_get_option"])
+                                "jj_plan_host_chunks", "jj_plan_msm_host_passes", "jj_msm_basis_info", "jj_plan_msm_basis", "jj_plan_msm_ragged", "jj_plan_msm_ragged_items",
+                                "jj_ctx_set_option", "jj_ctx_get_option"])
 
 _lib = None
 
@@ -179,6 +181,10 @@ def load():
     lib.jj_msm_basis_info.argtypes = [_vp, C.POINTER(C.c_int64)]
     lib.jj_plan_msm_basis.restype = C.c_int
     lib.jj_plan_msm_basis.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int64)]
+    lib.jj_plan_msm_ragged.restype = C.c_int
+    lib.jj_plan_msm_ragged.argtypes = [C.c_size_t, _vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int64)]
+    lib.jj_plan_msm_ragged_items.restype = C.c_int
+    lib.jj_plan_msm_ragged_items.argtypes = [C.c_size_t, _vp, C.c_int, C.c_int, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.jj_ctx_set_option.restype = C.c_int
     lib.jj_ctx_set_option.argtypes = [_vp, C.c_char_p, C.c_longlong]
     lib.jj_ctx_get_option.restype = C.c_int

@@ -206,6 +206,11 @@ struct jj_ctx {
   int msm_small_blk = 4;         // small-batch path: at most this many 64-quad workgroups per window (JJ_MSM_SMALL_BLK, 1..64; 4 x 64 windows = one per CU)
   int msm_windows = 0;           // number of windows W (0 = from n; JJ_MSM_WINDOWS, 16..36: the two-pass sort holds at most 128 coarse bins per window, i.e. windows of at most 16 bits)
   int msm_small_max = 1 << 14;   // batches up to this size take the two-launch small-batch path (JJ_MSM_SMALL_MAX; 0 = never)
+  // jj_msm_ragged's planner (msm_ragged_plan, jj_msm.hip): terms per slice at least, waves the short segments' terms are cut for, terms per round of
+  // tables (options msm_ragged_slice_min 1..8192, msm_ragged_waves 1..65536, msm_ragged_round_terms 1..2^18; the same results for every value)
+  int msm_ragged_slice_min = 16, msm_ragged_waves = 2048, msm_ragged_round_terms = 1 << 18;
+  // jj_msm_ragged's work list on its way to the device: page-locked, owned by the context; ragged_ev = the copy of the last list has read it
+  uint8_t* ragged_host = nullptr; size_t ragged_host_cap = 0; hipEvent_t ragged_ev = nullptr; bool ragged_in_flight = false;
   bool torsion_ladder = false;   // subgroup test: false = Tate pairing (k_torsion_free), true = multiply by r (reference definition)
   bool fb_const_time = true;     // fixed-base window select: true = lane-staged + ds_bpermute shuffle, false = per-lane LDS gather
   int fb_default_kind = 7;       // what window_bits = 0 means: 7 = signed comb (32 additions + 3 doublings), 6 = signed 6-bit windows (43 additions); JJ_FIXEDBASE_DEFAULT

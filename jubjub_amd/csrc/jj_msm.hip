@@ -534,6 +534,185 @@ JJ_API int jj_msm_batch(jj_ctx* c, size_t B, size_t n, const void* scalars, cons
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
 }
+// ---- S independent MSMs of different lengths over consecutive runs of one term array (jj_msm_ragged).  Segments of up to MSM_BATCH_MAX
+// terms, the short ones, run through k_msm_ragged_sum / _finish (jj_msm_kernels.h) from a work list the planner below writes; longer ones are
+// MSM jobs as in msm_batch_jobs.  The planner is a pure function of the offsets (jj_plan_msm_ragged, jj_plan_msm_ragged_items):
+//   slice length  t = max(slice_min, ceil(N_short / waves)), N_short = the terms of the short segments: about `waves` waves in all, none below
+//                 slice_min terms unless its segment is shorter (the reasoning of MSM_BATCH_WAVES / MSM_BATCH_SLICE_MIN)
+//   slices        a short segment of len terms: ceil(len / t) slices of floor(len / slices) or one more terms; an empty segment: none
+//   rounds        whole short segments, consecutive in input order, as long as their terms stay within round_terms (one table of 1296 B per term);
+//                 a segment above round_terms has a round of its own.  A round's terms are contiguous: a long segment closes the round before it
+//                 (it belongs to none), so that k_msm_batch_tables runs over one range and builds no table the sums never read.
+struct RaggedRound { uint64_t t0, t1; size_t item0, item1, seg0, seg1, parts; };      // terms | items | non-empty short segments (counted over the call) | parked partial sums
+struct RaggedPlan { uint64_t t = 0; size_t short_segs = 0, long_segs = 0, items = 0; std::vector<RaggedRound> rounds; };
+// emit(round, segment, position of the segment among the round's non-empty segments, first term, end term, slices, slice, part0)
+template <class Emit>
+static void msm_ragged_plan(size_t S, const uint64_t* off, uint64_t slice_min, uint64_t waves, uint64_t round_terms, RaggedPlan& P, Emit emit) {
+  uint64_t n_short = 0;
+  for (size_t s = 0; s < S; s++) { const uint64_t len = off[s + 1] - off[s]; if (len <= MSM_BATCH_MAX) n_short += len; }
+  const uint64_t t = std::max<uint64_t>(std::max<uint64_t>(slice_min, 1), (n_short + waves - 1) / waves);
+  P.t = t;
+  bool open = false;
+  for (size_t s = 0; s < S; s++) {
+    const uint64_t lo = off[s], len = off[s + 1] - lo;
+    if (len == 0) continue;
+    if (len > MSM_BATCH_MAX) { P.long_segs++; open = false; continue; }
+    if (!open || P.rounds.back().t1 - P.rounds.back().t0 + len > round_terms) { P.rounds.push_back(RaggedRound{lo, lo, P.items, P.items, P.short_segs, P.short_segs, 0}); open = true; }
+    RaggedRound& r = P.rounds.back();
+    const uint64_t k = (len + t - 1) / t, base = len / k, rem = len % k;
+    uint64_t first = lo;
+    for (uint64_t j = 0; j < k; j++) {
+      const uint64_t end = first + base + (j < rem ? 1 : 0);
+      emit(P.rounds.size() - 1, s, r.seg1 - r.seg0, first, end, k, j, r.parts);
+      first = end;
+    }
+    if (k > 1) r.parts += (size_t)k;
+    P.items += (size_t)k; r.item1 = P.items;
+    P.short_segs++; r.seg1 = P.short_segs;
+    r.t1 = lo + len;
+  }
+}
+// offsets[0] = 0, non-decreasing, and S, N whose byte counts fit size_t
+static bool msm_ragged_offsets_ok(size_t S, const uint64_t* off) {
+  if (S >= SIZE_MAX / 64 || off[0] != 0) return false;
+  for (size_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return false;
+  return off[S] <= SIZE_MAX / 64;
+}
+static bool msm_ragged_plan_args(size_t S, const uint64_t* off, int& slice_min, int& waves, uint64_t& round_terms) {
+  if (slice_min < 0 || waves < 0 || (S && !off) || (S && !msm_ragged_offsets_ok(S, off))) return false;
+  if (!slice_min) slice_min = (int)MSM_BATCH_SLICE_MIN;
+  if (!waves) waves = (int)MSM_BATCH_WAVES;
+  if (!round_terms) round_terms = MSM_BATCH_TABLE_TERMS;
+  return true;
+}
+JJ_API int jj_plan_msm_ragged(size_t S, const uint64_t* offsets, int slice_min, int waves, uint64_t round_terms, int64_t out[4]) {
+  if (!out || !msm_ragged_plan_args(S, offsets, slice_min, waves, round_terms)) return JJ_ERR_INVALID;
+  RaggedPlan P;
+  msm_ragged_plan(S, offsets, (uint64_t)slice_min, (uint64_t)waves, round_terms, P, [](size_t, size_t, size_t, uint64_t, uint64_t, uint64_t, uint64_t, size_t) {});
+  out[0] = (int64_t)P.short_segs; out[1] = (int64_t)P.long_segs; out[2] = (int64_t)P.items; out[3] = (int64_t)P.rounds.size();
+  return JJ_OK;
+}
+JJ_API int jj_plan_msm_ragged_items(size_t S, const uint64_t* offsets, int slice_min, int waves, uint64_t round_terms, uint64_t* items, size_t cap, size_t* count) {
+  if (!count || (cap && !items) || !msm_ragged_plan_args(S, offsets, slice_min, waves, round_terms)) return JJ_ERR_INVALID;
+  RaggedPlan P;
+  msm_ragged_plan(S, offsets, (uint64_t)slice_min, (uint64_t)waves, round_terms, P, [](size_t, size_t, size_t, uint64_t, uint64_t, uint64_t, uint64_t, size_t) {});
+  *count = P.items;
+  if (P.items > cap) return items ? JJ_ERR_INVALID : JJ_OK;          // cap = 0: the count only
+  size_t k = 0;
+  RaggedPlan Q;
+  msm_ragged_plan(S, offsets, (uint64_t)slice_min, (uint64_t)waves, round_terms, Q, [&](size_t round, size_t s, size_t, uint64_t first, uint64_t end, uint64_t, uint64_t, size_t) {
+    uint64_t* it = items + 4 * k++;
+    it[0] = round; it[1] = s; it[2] = first; it[3] = end;
+  });
+  return JJ_OK;
+}
+// the short segments of a planned call: device arrays ds / dp (all N terms), results to their rows of dout; all on the context's stream.
+// Workspaces of lane 0 as msm_batch_enqueue's (buf[1] tables, buf[2] window sums, buf[3] parked partial sums, buf[4] per-segment counters) and
+// buf[6]: the work list (items, then the output row of every non-empty short segment).  The list is written into page-locked memory of the
+// context and copied from there by the stream: the call may return before the copy runs, so the next call waits for ragged_ev before it
+// writes the next list.
+static int msm_ragged_enqueue(jj_ctx* c, size_t S, const uint64_t* off, const uint8_t* ds, const uint8_t* dp, uint8_t* dout) {
+  MsmLane& L = c->lanes[0];
+  MsmParams mp;
+  msm_layout(mp, SM_W, 0, 1);
+  const uint64_t slice_min = (uint64_t)c->msm_ragged_slice_min, waves = (uint64_t)c->msm_ragged_waves, round_terms = (uint64_t)c->msm_ragged_round_terms;
+  RaggedPlan P;
+  msm_ragged_plan(S, off, slice_min, waves, round_terms, P, [](size_t, size_t, size_t, uint64_t, uint64_t, uint64_t, uint64_t, size_t) {});
+  if (!P.items) return JJ_OK;
+  const size_t TAB = (size_t)SM_SLOTS * ENIELS_WORDS * 4, SUMS = (size_t)SM_W * MSM_BATCH_PT_WORDS * 4;
+  const size_t map_off = P.items * sizeof(RaggedItem), list_bytes = map_off + P.short_segs * 8;
+  size_t terms = 0, segs = 0, parts = 0;
+  for (const RaggedRound& r : P.rounds) { terms = std::max<size_t>(terms, (size_t)(r.t1 - r.t0)); segs = std::max(segs, r.seg1 - r.seg0); parts = std::max(parts, r.parts); }
+  int rc;
+  if ((rc = ensure(c, L.buf[1], terms * TAB)) || (rc = ensure(c, L.buf[2], std::min(segs, MSM_BATCH_ROWS) * SUMS)) || (rc = ensure(c, L.buf[6], list_bytes))) return rc;
+  if (parts && ((rc = ensure(c, L.buf[3], parts * SUMS)) || (rc = ensure(c, L.buf[4], segs * 4)))) return rc;
+  if (!c->ragged_ev) HIPCHK(c, hipEventCreateWithFlags(&c->ragged_ev, hipEventDisableTiming));
+  if (c->ragged_in_flight) { HIPCHK(c, hipEventSynchronize(c->ragged_ev)); c->ragged_in_flight = false; }     // the previous list has left the host buffer
+  if (c->ragged_host_cap < list_bytes) {
+    if (c->ragged_host) (void)hipHostFree(c->ragged_host);
+    c->ragged_host = nullptr; c->ragged_host_cap = 0;
+    const size_t want = std::max<size_t>(list_bytes + list_bytes / 2, 1 << 16);
+    if (hipHostMalloc((void**)&c->ragged_host, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); c->ragged_host = nullptr; c->err = "hipHostMalloc(work list) failed"; return JJ_ERR_NOMEM; }
+    c->ragged_host_cap = want;
+  }
+  RaggedItem* items = (RaggedItem*)c->ragged_host;
+  uint64_t* rowmap = (uint64_t*)(c->ragged_host + map_off);
+  std::vector<size_t> group_item;                       // first item of every finish group (MSM_BATCH_ROWS segments of a round), round after round
+  {
+    RaggedPlan Q;
+    size_t k = 0;
+    msm_ragged_plan(S, off, slice_min, waves, round_terms, Q, [&](size_t round, size_t s, size_t seg, uint64_t first, uint64_t end, uint64_t slices, uint64_t slice, size_t part0) {
+      const uint64_t t0 = P.rounds[round].t0;
+      if (slice == 0) { rowmap[P.rounds[round].seg0 + seg] = s; if (seg % MSM_BATCH_ROWS == 0) group_item.push_back(k); }
+      items[k++] = RaggedItem{(u32)seg, (u32)(first - t0), (u32)(end - t0), (u32)slices, (u32)part0, (u32)slice, {0, 0}};
+    });
+  }
+  HIPCHK(c, hipMemcpyAsync(L.buf[6].p, c->ragged_host, list_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ragged_ev, c->stream));
+  c->ragged_in_flight = true;
+  const RaggedItem* ditems = (const RaggedItem*)L.buf[6].p;
+  const unsigned long long* dmap = (const unsigned long long*)((const uint8_t*)L.buf[6].p + map_off);
+  u32* tables = (u32*)L.buf[1].p; u32* sums = (u32*)L.buf[2].p;
+  size_t g = 0;
+  for (const RaggedRound& r : P.rounds) {
+    const size_t rt = (size_t)(r.t1 - r.t0), rsegs = r.seg1 - r.seg0;
+    hipLaunchKernelGGL(k_msm_batch_tables, dim3(blocks_for(4 * rt)), dim3(256), 0, c->stream, rt, (const void*)(dp + r.t0 * 64), tables);
+    if (r.parts) HIPCHK(c, hipMemsetAsync(L.buf[4].p, 0, rsegs * 4, c->stream));
+    for (size_t s0 = 0; s0 < rsegs; s0 += MSM_BATCH_ROWS, g++) {
+      const size_t gn = std::min(MSM_BATCH_ROWS, rsegs - s0), i0 = group_item[g], i1 = s0 + gn < rsegs ? group_item[g + 1] : r.item1;
+      hipLaunchKernelGGL(k_msm_ragged_sum, dim3((unsigned)(i1 - i0)), dim3(64), 0, c->stream, ditems + i0, (u32)s0, (const void*)(ds + r.t0 * 32), (const u32*)tables, mp,
+                         (u32*)L.buf[3].p, (u32*)L.buf[4].p, sums);
+      hipLaunchKernelGGL(k_msm_ragged_finish, dim3(blocks_for(gn, MSM_BATCH_FINISH_ROWS)), dim3(64), 0, c->stream, (u32)gn, mp, (const u32*)sums, dmap + r.seg0 + s0, (void*)dout);
+    }
+  }
+  return JJ_OK;
+}
+JJ_API int jj_msm_ragged(jj_ctx* c, size_t S, const uint64_t* offsets, const void* scalars, const void* points, void* out64) {
+  if (!c) return JJ_ERR_INVALID;
+  if (S == 0) return JJ_OK;
+  if (!offsets || !out64 || is_device_ptr(offsets) || !msm_ragged_offsets_ok(S, offsets)) return JJ_ERR_INVALID;
+  const size_t N = (size_t)offsets[S];
+  if (N && (!scalars || !points)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  size_t empty = 0;
+  std::vector<size_t> longs;                            // the segments of the jobs route
+  for (size_t s = 0; s < S; s++) { const uint64_t len = offsets[s + 1] - offsets[s]; if (!len) empty++; else if (len > MSM_BATCH_MAX) longs.push_back(s); }
+  int rc; OutRef o;
+  const void *ds = nullptr, *dp = nullptr;
+  if ((rc = stage_in(c, 0, scalars, 32 * N, &ds))) return rc;
+  if ((rc = stage_in(c, 1, points, 64 * N, &dp))) return rc;
+  if ((rc = stage_out(c, c->out[0], out64, 64 * S, &o))) return rc;
+  if (empty) {
+    // the identity (0, 1) in every row; the finish launches and the jobs then write the rows of the non-empty segments
+    HIPCHK(c, hipMemsetAsync(o.dev, 0, S * 64, c->stream));
+    HIPCHK(c, hipMemset2DAsync((uint8_t*)o.dev + 32, 64, 1, 1, S, c->stream));
+  }
+  if ((rc = msm_ragged_enqueue(c, S, offsets, (const uint8_t*)ds, (const uint8_t*)dp, (uint8_t*)o.dev))) return rc;
+  // long segments: one MSM job each over the staged arrays, a few in flight (the host tail of one beside the kernels of the next)
+  std::vector<uint8_t> res(longs.size() * 64);
+  if (!longs.empty()) {
+    const size_t depth = 2 * (size_t)std::max(1, c->msm_lanes);
+    std::vector<std::pair<jj_msm_job*, size_t>> q;
+    size_t head = 0;
+    auto finish_one = [&]() { const auto& f = q[head++]; const int r = jj_msm_finish(f.first, res.data() + 64 * f.second); if (!rc) rc = r; };
+    for (size_t k = 0; k < longs.size() && !rc; k++) {
+      const uint64_t lo = offsets[longs[k]], len = offsets[longs[k] + 1] - lo;
+      jj_msm_job* j = nullptr;
+      const int r = msm_begin_locked(c, (size_t)len, (const uint8_t*)ds + lo * 32, (const uint8_t*)dp + lo * 64, 0, 1, true, &j);
+      if (r) { rc = r; break; }
+      q.emplace_back(j, k);
+      if (q.size() - head > depth) finish_one();
+    }
+    while (head < q.size()) finish_one();                 // every job is finished (and released), also after a failure
+    if (rc) return rc;
+    if (!o.host) for (size_t k = 0; k < longs.size(); k++) HIPCHK(c, hipMemcpyAsync((uint8_t*)o.dev + longs[k] * 64, res.data() + 64 * k, 64, hipMemcpyHostToDevice, c->stream));
+  }
+  bool sync = !longs.empty();
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  if ((rc = finish(c, sync))) return rc;
+  if (o.host) for (size_t k = 0; k < longs.size(); k++) memcpy((uint8_t*)out64 + longs[k] * 64, res.data() + 64 * k, 64);
+  return JJ_OK;
+}
 // ---- fixed-basis MSM (jj_msm_basis_*): the points are handed over once, every call brings scalars only.  A basis keeps, in the memory of its
 // device, the tables {0 .. 8} P of its first min(n, MSM_BATCH_MAX) points (rows of up to MSM_BATCH_MAX terms run through k_msm_batch_sum /
 // _finish over them, whatever B is) and, when it has more points than that, the gathered-Niels records of all of them: one per point (mode 1:

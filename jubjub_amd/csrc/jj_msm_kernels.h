@@ -326,6 +326,94 @@ __global__ void __launch_bounds__(64) k_msm_batch_finish(u32 rows, MsmParams mp,
   }
 }
 
+// ================================================================================================ ragged batches (jj_msm_ragged)
+// S independent sums of DIFFERENT lengths over consecutive runs of one term array.  The host's planner (msm_ragged_plan, jj_msm.hip) cuts
+// every non-empty segment of a round into slices of at most t terms and writes one work item per slice; the tables {0 .. 8} P of the round's
+// terms are k_msm_batch_tables' over the round's contiguous term range, indexed by the term's position in the round.
+// k_msm_ragged_sum: ONE WAVE per work item, ONE LANE per window: k_msm_batch_sum's loop over the item's terms [first, end).  The item is
+// read through blockIdx.x -- a wave-uniform address, so the item, like the scalar words of every term, stays on the scalar path.  A segment
+// with one slice writes its 64 window sums; a segment with several parks them at part[part0 + slice], and the last slice of THAT SEGMENT to
+// arrive (counters[seg], zero on entry) adds the others lane by lane -- the fence / counter discipline of k_msm_batch_sum.
+// k_msm_ragged_finish: k_msm_batch_finish's chain (a quad per segment, Horner over the 64 windows, one inversion); the result goes to row
+// rowmap[segment] of out64: empty segments and segments of the jobs route have no entry and are never written here.
+struct RaggedItem {
+  u32 seg;        // the segment, counted over the round's non-empty segments
+  u32 first, end; // the slice's terms, as positions in the round
+  u32 slices;     // slices of the segment
+  u32 part0;      // slices > 1: the segment's first parked partial sum (this slice's: part0 + slice)
+  u32 slice;
+  u32 pad[2];
+};
+static_assert(sizeof(RaggedItem) == 32, "one work item is two 16-byte loads");
+// grid: one 64-lane workgroup per item of items[]; sums: row seg - seg0 (the finish group's first segment); scalars / tables: the round's
+__global__ void __launch_bounds__(64) k_msm_ragged_sum(const RaggedItem* __restrict__ items, u32 seg0, const void* __restrict__ scalars, const u32* __restrict__ tables,
+                                                       MsmParams mp, u32* __restrict__ part, u32* __restrict__ counters, u32* __restrict__ sums) {
+  const u32 lane = threadIdx.x;
+  const RaggedItem it = items[blockIdx.x];
+  const u32 lo = it.first, hi = it.end, slices = it.slices;
+  // digit of this lane's window in the (wave-uniform) recoded scalar of term i, and the address of its entry
+  auto entry = [&](u32 i, u32& neg) -> const u32* {
+    u32 k[8];
+    load8(k, scalars, i);
+    msm_recode(k, mp);
+    const u32 a = msm_digit_reg(k, mp, (int)lane, neg);
+    return tables + ((size_t)i * SM_SLOTS + a) * (size_t)ENIELS_WORDS;
+  };
+  Ext acc = Curve::identity();
+  u32 neg = 0;
+  ENiels e = Curve::eniels_identity();
+  if (lo < hi) e = load_eniels(entry(lo, neg));
+  #pragma unroll 1
+  for (u32 i = lo; i < hi; i++) {
+    const ENiels cur = e;
+    const u32 cmask = neg ? ~0u : 0u;
+    if (i + 1 < hi) e = load_eniels(entry(i + 1, neg));
+    acc = Curve::add_signed<true>(acc, cur, cmask);
+  }
+  Fe T = Curve::tt<true>(acc);
+  if (slices > 1) {
+    __shared__ u32 last_s;
+    u32* mine = part + (size_t)it.part0 * SM_W * MSM_BATCH_PT_WORDS;
+    msm_batch_put(mine + (size_t)it.slice * SM_W * MSM_BATCH_PT_WORDS, lane, acc, T);
+    __threadfence();
+    __syncthreads();
+    if (lane == 0) last_s = atomicAdd(&counters[it.seg], 1u) == slices - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!last_s) return;
+    __threadfence();
+    #pragma unroll 1
+    for (u32 s = 0; s < slices; s++) {
+      if (s == it.slice) continue;
+      Fe Tq;
+      const Ext q = msm_batch_get(mine + (size_t)s * SM_W * MSM_BATCH_PT_WORDS, lane, Tq);
+      acc = Curve::add<true>(acc, Curve::to_niels_t(q, Tq));
+    }
+    T = Curve::tt<true>(acc);
+  }
+  msm_batch_put(sums + (size_t)(it.seg - seg0) * SM_W * MSM_BATCH_PT_WORDS, lane, acc, T);
+}
+// rows x 64 window sums -> canonical affine points at rows rowmap[0 .. rows) of out64
+__global__ void __launch_bounds__(64) k_msm_ragged_finish(u32 rows, MsmParams mp, const u32* __restrict__ sums, const unsigned long long* __restrict__ rowmap, void* out64) {
+  const u32 role = threadIdx.x & 3u, row = blockIdx.x * MSM_BATCH_FINISH_ROWS + (threadIdx.x >> 2);
+  if (row >= rows) return;                                  // whole quads leave together
+  const u32* src = sums + (size_t)row * SM_W * MSM_BATCH_PT_WORDS;
+  Fe T;
+  Ext acc = msm_batch_get(src, SM_W - 1, T);
+  #pragma unroll 1
+  for (int w = SM_W - 2; w >= 0; w--) {
+    const int width = msm_win_width(mp, w);
+    #pragma unroll 1
+    for (int i = 0; i < width; i++) acc = quad_dbl_t(acc, role, T);
+    Fe Tp, dummy;
+    const Ext p = msm_batch_get(src, (u32)w, Tp);
+    acc = quad_add_ext_t(acc, T, p, Tp, role, T, Tp, Tp, dummy);
+  }
+  if (role == 0) {
+    const Fe zi = Fq::invert(acc.z);
+    store_affine(out64, (size_t)rowmap[row], Fq::mul(acc.u, zi), Fq::mul(acc.v, zi));
+  }
+}
+
 // ================================================================================================ Pippenger: conversion
 // recode scalars (k' word-major) and convert points to affine-Niels AoS (27 words in a 128-byte record)
 // what: 1 = scalars, 2 = points, 3 = both (the two halves are independent: the sort needs only the scalars, so the host may run

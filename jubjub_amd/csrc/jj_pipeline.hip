@@ -401,6 +401,11 @@ static const CtxOption* ctx_options() {
     {"pipe_chunk_log2", 0, 24, [](jj_ctx* c, long long v) { c->pipe_chunk = v >= 8 ? (size_t)1 << v : 0; }, [](const jj_ctx* c) { long long l = 0; while (((size_t)1 << l) < c->pipe_chunk) l++; return c->pipe_chunk ? l : 0LL; }},
     {"fixedbase_default", 6, 7, [](jj_ctx* c, long long v) { c->fb_default_kind = (int)v; }, [](const jj_ctx* c) { return (long long)c->fb_default_kind; }},
     JJ_OPT("vb_mul2_window", 4, 5, vb_mul2_window, int),                     // jj_varbase_mul2_*: signed window width; the same results, 4 = half the table workspace (2592 B per lane)
+    // jj_msm_ragged's planner (msm_ragged_plan, jj_msm.hip): every value gives the same results, ranges in the header; their parity is held by
+    // tests/test_gpu_msm_ragged.py over a ragged corpus (the matrix of tests/planner_matrix.py runs jj_msm's corpus, which never reaches them)
+    JJ_OPT("msm_ragged_slice_min", 1, 8192, msm_ragged_slice_min, int),      // terms per slice (one wave) at least
+    JJ_OPT("msm_ragged_waves", 1, 65536, msm_ragged_waves, int),             // waves the short segments' terms are cut for
+    JJ_OPT("msm_ragged_round_terms", 1, 1 << 18, msm_ragged_round_terms, int), // terms per round of tables (1296 B each)
     // planner overrides (tests and measurements; every value gives the same results)
     JJ_OPT("msm_windows", 0, MSM_WINDOWS_MAX, msm_windows, int),             // 0 = from n; else 16..36
     JJ_OPT("msm_small_max", 0, 1 << 20, msm_small_max, int),
@@ -530,6 +535,8 @@ JJ_API int jj_ctx_destroy(jj_ctx* c) {
   if (c->gather_dev.p) (void)hipFree(c->gather_dev.p);
   if (c->poison_dev.p) (void)hipFree(c->poison_dev.p);
   if (c->gather_host) (void)hipHostFree(c->gather_host);
+  if (c->ragged_host) (void)hipHostFree(c->ragged_host);
+  if (c->ragged_ev) (void)hipEventDestroy(c->ragged_ev);
   if (c->pipe.ready) {
     for (int i = 0; i < 2; i++) {
       (void)hipEventDestroy(c->pipe.ev_in[i]); (void)hipEventDestroy(c->pipe.ev_done[i]); (void)hipEventDestroy(c->pipe.ev_out[i]);

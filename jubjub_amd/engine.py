@@ -68,6 +68,39 @@ def _msm_batch_shapes(scalars, points):
     raise ValueError("points: shape (%d, 64) (shared) or (%d, %d, 64) expected, got %r" % (n, B, n, ps))
 
 
+def _ragged_offsets(offsets):
+    """offsets of jj_msm_ragged as a contiguous host uint64 array"""
+    if _is_torch(offsets):
+        offsets = offsets.cpu().numpy()
+    o = np.asarray(offsets)
+    if o.ndim != 1 or o.size == 0:
+        raise ValueError("offsets: a sequence of S + 1 >= 1 integers expected")
+    if o.dtype.kind not in "iu":
+        raise ValueError("offsets: integers expected, got %s" % o.dtype)
+    if o.dtype.kind == "i" and (o < 0).any():
+        raise ValueError("offsets: negative value")
+    o = np.ascontiguousarray(o, dtype=np.uint64)
+    if o[0] != 0:
+        raise ValueError("offsets[0] must be 0, got %d" % int(o[0]))
+    if (o[1:] < o[:-1]).any():
+        raise ValueError("offsets must be non-decreasing")
+    return o
+
+
+def _msm_ragged_shapes(scalars, points, offsets):
+    """(S, N) of jj_msm_ragged's arguments: scalars (N, 32); points (N, 64); offsets: S + 1 integers, offsets[0] = 0, non-decreasing,
+    offsets[-1] = N"""
+    ss, ps = tuple(scalars.shape), tuple(points.shape)
+    if len(ss) != 2 or ss[1] != 32:
+        raise ValueError("scalars: shape (N, 32) expected, got %r" % (ss,))
+    if ps != (ss[0], 64):
+        raise ValueError("points: shape (%d, 64) expected, got %r" % (ss[0], ps))
+    o = _ragged_offsets(offsets)
+    if int(o[-1]) != ss[0]:
+        raise ValueError("offsets[-1] = %d, but there are %d terms" % (int(o[-1]), ss[0]))
+    return o.size - 1, ss[0]
+
+
 _MSM_BASIS_MODES = {"auto": 0, "points": 1, "windows": 2, 0: 0, 1: 1, 2: 2}
 
 
@@ -526,6 +559,44 @@ class Engine:
         self._bind_stream([a, p])
         self._check(self._lib.jj_msm_batch(self._ctx, C.c_size_t(B), C.c_size_t(n), a.ptr, p.ptr, C.c_int(shared), optr))
         return out
+
+    def msm_ragged(self, scalars, points, offsets, out=None):
+        """S independent MSMs of different lengths in one call (jj_msm_ragged): row s = msm(scalars[offsets[s]:offsets[s + 1]], points[the same]).
+        scalars (N, 32), points (N, 64): numpy arrays or torch CUDA tensors; offsets: S + 1 integers (any sequence or array; kept on the host),
+        offsets[0] = 0, non-decreasing, offsets[-1] = N; returns (S, 64) of the scalars' kind, an empty segment giving the identity.  With torch
+        tensors and segments of up to 8192 terms the call only queues the work.  `out`: a caller-owned (S, 64) array of the scalars' kind."""
+        S, N = _msm_ragged_shapes(scalars, points, offsets)
+        o = _ragged_offsets(offsets)
+        a, p = _Arg(scalars, 32), _Arg(points, 64)
+        if out is None:
+            out, optr = self._alloc(a, S, 64)
+        else:
+            oa = _Arg(out, 64)
+            if oa.n != S or oa.torch != a.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x 64 bytes of the scalars' kind expected" % S)
+            optr = oa.ptr
+        self._bind_stream([a, p])
+        self._check(self._lib.jj_msm_ragged(self._ctx, C.c_size_t(S), o.ctypes.data, a.ptr, p.ptr, optr))
+        return out
+
+    def plan_msm_ragged(self, offsets, slice_min=0, waves=0, round_terms=0, items=False):
+        """What msm_ragged does with these offsets (jj_plan_msm_ragged; no device work): {"short", "long", "items", "rounds"}; 0 = the default
+        of slice_min / waves / round_terms (16 / 2048 / 2^18; this context's options are NOT read).  items=True adds "list": an (items, 4)
+        uint64 array of (round, segment, first term, end term)."""
+        o = _ragged_offsets(offsets)
+        lib = _lib.load()
+        out4 = (C.c_int64 * 4)()
+        if lib.jj_plan_msm_ragged(C.c_size_t(o.size - 1), o.ctypes.data, int(slice_min), int(waves), C.c_uint64(int(round_terms)), out4):
+            raise ValueError("jj_plan_msm_ragged refused its arguments")
+        plan = {"short": out4[0], "long": out4[1], "items": out4[2], "rounds": out4[3]}
+        if items:
+            arr = np.zeros((max(1, out4[2]), 4), dtype=np.uint64)
+            count = C.c_size_t()
+            if lib.jj_plan_msm_ragged_items(C.c_size_t(o.size - 1), o.ctypes.data, int(slice_min), int(waves), C.c_uint64(int(round_terms)),
+                                            arr.ctypes.data, C.c_size_t(arr.shape[0]), C.byref(count)):
+                raise ValueError("jj_plan_msm_ragged_items refused its arguments")
+            plan["list"] = arr[:count.value]
+        return plan
 
     def msm_basis(self, points, mode="auto", windows=0):
         """Hands a fixed set of points over once (jj_msm_basis_create): points (n, 64), numpy or torch CUDA; the array may be reused

@@ -146,6 +146,18 @@ impl Gpu {
         out.chunks_exact(64).map(|r| get_point(r).into()).collect()
     }
 
+    /// Sums of different lengths in one call (`jj_msm_ragged`): row `s` is `sum_i points[i] * scalars[i]` over `offsets[s] <= i < offsets[s + 1]`.
+    /// `offsets` holds `S + 1` values, starts at 0, never decreases and ends at `points.len()`; an empty run gives the identity.
+    pub fn msm_ragged(&self, points: &[AffinePoint], scalars: &[Fr], offsets: &[u64]) -> Vec<ExtendedPoint> {
+        assert_eq!(points.len(), scalars.len());
+        if offsets.is_empty() { return Vec::new(); }
+        assert!(offsets[0] == 0 && offsets.windows(2).all(|w| w[0] <= w[1]) && *offsets.last().unwrap() == points.len() as u64);
+        let (rows, s, p) = (offsets.len() - 1, put_scalars(scalars), put_points(points));
+        let mut out = vec![0u8; 64 * rows];
+        assert_eq!(unsafe { jj_msm_ragged(self.0, rows, offsets.as_ptr(), s.as_ptr() as _, p.as_ptr() as _, out.as_mut_ptr() as _) }, 0);
+        out.chunks_exact(64).map(|r| get_point(r).into()).collect()
+    }
+
     /// `AffinePoint::batch_from_bytes` (src/lib.rs:541-627); `flags`: ZIP216 (from_bytes vs from_bytes_pre_zip216_compatibility,
     /// src/lib.rs:469-489), TORSION_FREE (SubgroupPoint::from_bytes, 1427-1429), NOT_SMALL_ORDER (699-705), CLEAR_COFACTOR (722-724).
     pub fn batch_from_bytes(&self, enc: &[[u8; 32]], flags: u32) -> Vec<Option<AffinePoint>> {
