@@ -84,6 +84,32 @@ struct Fe {
 #ifndef JJ_OPAQUE_MODE
 #define JJ_OPAQUE_MODE 1
 #endif
+// Field::invert_divsteps: the modulus regrouped into 9 signed limbs of 30 bits (one batch of divsteps shifts by exactly one such limb) and
+// p^-1 mod 2^30, both built at compile time from P::P.
+constexpr int DS_LB = 30;                      // limb width inside invert_divsteps = divsteps per batch
+constexpr u32 DS_MASK = 0x3fffffffu;
+// Bernstein-Yang, "Fast constant-time gcd computation and modular inversion" (TCHES 2019(3)), Theorem 11.2: for 0 <= g < f < 2^d, f odd,
+// floor((49 d + 57) / 17) divsteps from delta = 1 reach g = 0, f = +-gcd.  d = 256 (both moduli are below 2^255): 741, rounded up to whole batches.
+constexpr int DS_BATCHES = ((49 * 256 + 57) / 17 + DS_LB - 1) / DS_LB;   // 25 batches, 750 divsteps
+struct DsMod { int32_t p[NL]; u32 pinv; };
+template <class P>
+constexpr DsMod make_dsmod() {
+  DsMod m{};
+  for (int i = 0; i < NL; i++) {
+    u32 v = 0;
+    for (int b = 0; b < DS_LB; b++) {
+      const int bit = DS_LB * i + b, li = bit / LB, lo = bit % LB;
+      if (li < NL) v |= ((P::P[li] >> lo) & 1u) << b;
+    }
+    m.p[i] = (int32_t)v;
+  }
+  const u32 p0 = (u32)m.p[0] | ((u32)m.p[1] << DS_LB);
+  u32 x = p0;                                                // p odd: p * p = 1 mod 8; each Newton step doubles the correct bits
+  for (int k = 0; k < 5; k++) x *= 2u - p0 * x;
+  m.pinv = x & DS_MASK;
+  return m;
+}
+
 template <class P, int PIN = JJ_MUL_PIN>
 struct Field {
   static constexpr u32 PINV = (0u - P::NINV) & LMASK;   // p^-1 mod 2^29 (1 for Fq: p = 1 mod 2^32)
@@ -375,6 +401,138 @@ static __device__ __forceinline__ u32 jj_opaque_asm(u32 x) { asm("" : "+v"(x)); 
   }
   // reference Fr::invert src/fr.rs:438-540 : a^(p-2); returns 0 when a == 0
   static JJ_DEV Fe invert(const Fe& a) { return pow_const<8, P::PM2>(a); }
+
+  // ---------------------------------------------------------------- inversion by divsteps
+  // The same value as invert (0 for 0, any in-contract input, a product-form result), by the constant-time "safegcd" of Bernstein and Yang
+  // instead of the power chain: about a third of the chain's instructions, and none of them depends on another lane.  Used where one
+  // inversion per lane is the whole serial chain of a kernel (k_normalize, k_varbase_mont_x1).
+  //   x = a / R in [0, p) (to_plain);  f = p, g = x, d = 0, e = 1 in 9 signed limbs of 30 bits;  invariant f = d x, g = e x (mod p).
+  //   DS_BATCHES times: 30 branch-free divsteps on the low words of f and g (delta = 1 at the start, kept as eta = -delta) give a
+  //   transition matrix (u v; q r) with 2^30 (f', g') = (u v; q r)(f, g) and |u| + |v|, |q| + |r| <= 2^30;  (f, g) takes that product
+  //   shifted down one limb (exact), (d, e) takes it plus the multiple of p that clears the low limb (p^-1 mod 2^30 is 1 for Fq, so its
+  //   digit is a mask) and, as long as d, e lie in (-2p, p), stays there.
+  //   Then g = 0, f = +-1 (f = p for x = 0) and sign(f) d = R / a;  the closing product by R^2 gives R^2 / a / R, the Montgomery form of 1/a.
+  // No load, store or branch depends on the data.  tests/cpp/emu_invert.cpp holds it to invert and checks the range of d, e at every batch.
+#ifdef JJ_HOST_EMU
+#define JJ_DS_ACC(name) i64 name = 0; __int128 name##_shadow = 0
+#define JJ_DS_MAD(name, x, y) do { name += (i64)(i32)(x) * (i64)(i32)(y); name##_shadow += (__int128)(i32)(x) * (__int128)(i32)(y); if (name##_shadow != (__int128)name) jj_emu_overflow("divsteps accumulator"); } while (0)
+#define JJ_DS_SHIFT(name) do { name >>= DS_LB; name##_shadow >>= DS_LB; } while (0)
+  // d in (-2p, p): the range update_de assumes and keeps
+  static bool ds_in_range(const i32 (&d)[NL], const DsMod& M) {
+    i64 lo = 0, hi = 0;                                    // signs of d + 2p and of d - p
+    for (int i = 0; i < NL; i++) { lo = (lo >> DS_LB) + d[i] + 2 * (i64)M.p[i]; hi = (hi >> DS_LB) + d[i] - (i64)M.p[i]; }
+    bool lo_zero = true; i64 c = 0;
+    for (int i = 0; i < NL; i++) { c = (c >> DS_LB) + d[i] + 2 * (i64)M.p[i]; if (i < NL - 1 ? (c & DS_MASK) != 0 : c != 0) lo_zero = false; }
+    return lo >= 0 && !lo_zero && hi < 0;
+  }
+#else
+#define JJ_DS_ACC(name) i64 name = 0
+#define JJ_DS_MAD(name, x, y) name += (i64)(i32)(x) * (i64)(i32)(y)
+#define JJ_DS_SHIFT(name) name >>= DS_LB
+#endif
+  static JJ_DEV Fe invert_divsteps(const Fe& a) {
+    constexpr DsMod M = make_dsmod<P>();
+    u32 w[8];
+    pack(w, to_plain(a));
+    i32 f[NL], g[NL], d[NL], e[NL];
+    _Pragma("unroll") for (int i = 0; i < NL; i++) {
+      const int bit = DS_LB * i, wi = bit >> 5, sh = bit & 31;
+      u32 v = w[wi] >> sh;
+      if (sh > 32 - DS_LB && wi + 1 < 8) v |= w[wi + 1] << (32 - sh);
+      g[i] = (i32)(v & DS_MASK);
+      f[i] = M.p[i]; d[i] = 0; e[i] = (i == 0);
+    }
+    u32 eta = ~0u;                                           // -delta
+    #pragma unroll 1
+    for (int batch = 0; batch < DS_BATCHES; batch++) {
+      // 30 divsteps: (delta, f, g) -> delta > 0 and g odd ? (1 - delta, g, (g - f)/2) : (1 + delta, f, (g + (g & 1) f)/2)
+      u32 u = 1, v = 0, q = 0, r = 1, fl = (u32)f[0], gl = (u32)g[0];
+      _Pragma("unroll") for (int s = 0; s < DS_LB; s++) {
+        u32 c1 = (u32)((i32)eta >> 31);                      // delta > 0
+        const u32 c2 = 0u - (gl & 1u);                       // g odd
+        gl += ((fl ^ c1) - c1) & c2; q += ((u ^ c1) - c1) & c2; r += ((v ^ c1) - c1) & c2;   // g += +-f, the matrix row with it
+        c1 &= c2;
+        eta = (eta ^ c1) - (c1 + 1u);                        // c1 ? -eta - 1 : eta - 1
+        fl += gl & c1; u += q & c1; v += r & c1;             // c1: f = the old g
+        gl >>= 1; u <<= 1; v <<= 1;
+      }
+      // what the middle-end knows about the entries and the limbs (sums of masked terms, non-negative masked limbs) must not reach the
+      // multiply-adds below, or single v_mad_i64_i32 are expanded and re-distributed (see mul_fips)
+      u = JJ_OPAQUE(u); v = JJ_OPAQUE(v); q = JJ_OPAQUE(q); r = JJ_OPAQUE(r);
+      // (d, e) <- ((u v; q r)(d, e) + (md, me) p) / 2^30
+      {
+        const u32 sd = (u32)(d[NL - 1] >> 31), se = (u32)(e[NL - 1] >> 31);
+        u32 md = (u & sd) + (v & se), me = (q & sd) + (r & se);         // a negative d or e brings one p along: keeps (-2p, p)
+        JJ_DS_ACC(cd); JJ_DS_ACC(ce);
+        const i32 d0 = (i32)JJ_OPAQUE((u32)d[0]), e0 = (i32)JJ_OPAQUE((u32)e[0]);
+        JJ_DS_MAD(cd, u, d0); JJ_DS_MAD(cd, v, e0);
+        JJ_DS_MAD(ce, q, d0); JJ_DS_MAD(ce, r, e0);
+        md -= (M.pinv * (u32)cd + md) & DS_MASK;
+        me -= (M.pinv * (u32)ce + me) & DS_MASK;
+        md = JJ_OPAQUE(md); me = JJ_OPAQUE(me);
+        JJ_DS_MAD(cd, M.p[0], md); JJ_DS_MAD(ce, M.p[0], me);
+#ifdef JJ_HOST_EMU
+        if (((u32)cd | (u32)ce) & DS_MASK) jj_emu_overflow("divsteps: low limb of the (d, e) update not cleared");
+#endif
+        JJ_DS_SHIFT(cd); JJ_DS_SHIFT(ce);
+        _Pragma("unroll") for (int i = 1; i < NL; i++) {
+          const i32 di = (i32)JJ_OPAQUE((u32)d[i]), ei = (i32)JJ_OPAQUE((u32)e[i]);
+          JJ_DS_MAD(cd, u, di); JJ_DS_MAD(cd, v, ei); JJ_DS_MAD(cd, M.p[i], md);
+          JJ_DS_MAD(ce, q, di); JJ_DS_MAD(ce, r, ei); JJ_DS_MAD(ce, M.p[i], me);
+          d[i - 1] = (i32)((u32)cd & DS_MASK); e[i - 1] = (i32)((u32)ce & DS_MASK);
+          JJ_DS_SHIFT(cd); JJ_DS_SHIFT(ce);
+        }
+        d[NL - 1] = (i32)cd; e[NL - 1] = (i32)ce;
+#ifdef JJ_HOST_EMU
+        if (cd != (i64)(i32)cd || ce != (i64)(i32)ce) jj_emu_overflow("divsteps: top limb of d, e");
+        if (!ds_in_range(d, M) || !ds_in_range(e, M)) jj_emu_overflow("divsteps: d or e left (-2p, p)");
+#endif
+      }
+      // (f, g) <- (u v; q r)(f, g) / 2^30, exact
+      {
+        JJ_DS_ACC(cf); JJ_DS_ACC(cg);
+        const i32 f0 = (i32)JJ_OPAQUE((u32)f[0]), g0 = (i32)JJ_OPAQUE((u32)g[0]);
+        JJ_DS_MAD(cf, u, f0); JJ_DS_MAD(cf, v, g0);
+        JJ_DS_MAD(cg, q, f0); JJ_DS_MAD(cg, r, g0);
+#ifdef JJ_HOST_EMU
+        if (((u32)cf | (u32)cg) & DS_MASK) jj_emu_overflow("divsteps: low limb of the (f, g) update not zero");
+#endif
+        JJ_DS_SHIFT(cf); JJ_DS_SHIFT(cg);
+        _Pragma("unroll") for (int i = 1; i < NL; i++) {
+          const i32 fi = (i32)JJ_OPAQUE((u32)f[i]), gi = (i32)JJ_OPAQUE((u32)g[i]);
+          JJ_DS_MAD(cf, u, fi); JJ_DS_MAD(cf, v, gi);
+          JJ_DS_MAD(cg, q, fi); JJ_DS_MAD(cg, r, gi);
+          f[i - 1] = (i32)((u32)cf & DS_MASK); g[i - 1] = (i32)((u32)cg & DS_MASK);
+          JJ_DS_SHIFT(cf); JJ_DS_SHIFT(cg);
+        }
+        f[NL - 1] = (i32)cf; g[NL - 1] = (i32)cg;
+#ifdef JJ_HOST_EMU
+        if (cf != (i64)(i32)cf || cg != (i64)(i32)cg) jj_emu_overflow("divsteps: top limb of f, g");
+#endif
+      }
+    }
+#ifdef JJ_HOST_EMU
+    { u32 o = 0; for (int i = 0; i < NL; i++) o |= (u32)g[i]; if (o) jj_emu_overflow("divsteps: g != 0 after the last batch"); }
+#endif
+    // sign(f) d, carried to limbs 0..7 in [0, 2^30) and a signed top limb, then regrouped into 29-bit limbs: value in (-2p, 2p)
+    const u32 sf = (u32)(f[NL - 1] >> 31);
+    u32 n[NL];
+    i32 c = 0;
+    _Pragma("unroll") for (int i = 0; i < NL - 1; i++) { const i32 t = (i32)(((u32)d[i] ^ sf) - sf) + c; n[i] = (u32)t & DS_MASK; c = t >> DS_LB; }
+    n[NL - 1] = (((u32)d[NL - 1] ^ sf) - sf) + (u32)c;
+    Fe x;
+    _Pragma("unroll") for (int i = 0; i < NL - 1; i++) {
+      const int bit = LB * i, j = bit / DS_LB, sh = bit % DS_LB;
+      u32 t = n[j] >> sh;
+      if (DS_LB - sh < LB) t |= n[j + 1] << (DS_LB - sh);
+      x.l[i] = t & LMASK;
+    }
+    x.l[NL - 1] = (n[NL - 2] >> (LB * (NL - 1) - DS_LB * (NL - 2))) + (n[NL - 1] << (DS_LB * (NL - 1) - LB * (NL - 1)));
+    return mul(x, konst(P::R2));
+  }
+#undef JJ_DS_ACC
+#undef JJ_DS_MAD
+#undef JJ_DS_SHIFT
 };
 
 typedef Field<FqP> Fq;

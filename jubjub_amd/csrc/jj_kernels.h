@@ -273,7 +273,7 @@ __global__ void __launch_bounds__(256) k_normalize(size_t n, size_t T, SoA ext, 
   // the running inverse is kept in PLAIN form (one product by the plain one per chunk): times a Montgomery-form prefix or Z it stays
   // plain, so 1/Z comes out plain and U/Z, V/Z go straight to plain integers (one product per coordinate, none for the conversion),
   // then two conditional additions of q
-  Fe inv = Fq::mul(Fq::invert(acc), Fq::plain_one());
+  Fe inv = Fq::mul(Fq::invert_divsteps(acc), Fq::plain_one());
   #pragma unroll 1
   for (int j = CHUNK - 1; j >= 0; j--) {
     const size_t i = t + (size_t)j * T;
@@ -682,7 +682,7 @@ __global__ void __launch_bounds__(256) k_varbase_mont_x1(size_t n, const void* p
     ext.put(2, i, acc);
     acc = Fq::mul(acc, den_of(i, num));
   }
-  Fe inv = Fq::invert(acc);
+  Fe inv = Fq::invert_divsteps(acc);
   #pragma unroll 1
   for (int s = MONT_X1_UNITS - 1; s >= 0; s--) {                 // backward: 1/d_s = inv * prefix_s, then inv *= d_s
     const size_t i = first + (size_t)s * 64;

@@ -7,7 +7,7 @@
 // order 2 (the group is cyclic of order 8r); d is not a square, so no other point is exceptional.
 //
 // Ladder: RFC 7748 section 5 (xDBLADD with a24 = (A - 2)/4 = 10240), bits 251..0 of the scalar (the reference's ladder skips the top
-// four, src/lib.rs:357-379), from (1 : 0) and (x1 : 1).  Per bit one masked swap keyed on bit_i ^ bit_(i+1) -- the bits of the Gray
+// four, src/lib.rs:357-379), from (1 : 0) and (x1 : 1).  Per bit one masked select of the doubling's two inputs keyed on bit_i ^ bit_(i+1) -- the bits of the Gray
 // code k ^ (k >> 1), shifted out of eight registers -- then 4S + 5M and one multiplication by a24 (mont_a24: 9 + 9 multiply-adds and
 // a carry, no product).  No load, store, branch or address of the loop depends on the scalar.
 // y-recovery: Okeya-Sakurai in the projective form of Costello-Smith ("Montgomery curves and their arithmetic", Algorithm 5), every
@@ -45,15 +45,21 @@ static JJ_DEV Fe mont_a24(const Fe& e) {
   return r;
 }
 
-// (x2 : z2) <- 2 (x2 : z2),  (x3 : z3) <- (x2 : z2) + (x3 : z3), difference (ox1 : 1); ox1 is already hidden (Field::opaque).
-// Inputs and outputs are products ("N"); the two sums that are squared get one carry step (tools/bounds_check.py mont_ladder).
-static JJ_DEV void mont_xdbladd(const Fe& ox1, Fe& x2, Fe& z2, Fe& x3, Fe& z3) {
+// One ladder step without swapping the state: with sw all-ones the roles of (x2 : z2) and (x3 : z3) are exchanged, which exchanges
+// DA = (x3 - z3)(x2 + z2) and CB = (x3 + z3)(x2 - z2) and so leaves DA + CB and (DA - CB)^2 as they are: only the doubling reads the
+// swap bit, through two selects (the sum and the difference it squares).  (x2 : z2) <- 2 (sw ? (x3 : z3) : (x2 : z2)),
+// (x3 : z3) <- (x2 : z2) + (x3 : z3), difference (ox1 : 1); ox1 is already hidden (Field::opaque).  The state that leaves is the one a
+// masked swap of all four coordinates followed by RFC 7748's xDBLADD leaves.  Inputs and outputs are products ("N"); the two sums that
+// are squared get one carry step, DA and CB multiply a difference by an uncarried sum (tools/bounds_check.py mont_ladder).
+// The four sums are hidden once and multiplied as they are (mul_hidden), and the select is hidden before its carry: hipcc otherwise
+// re-expands it inside the carry's mask (v_and + two v_bitop3_b32 per limb), or spills (tests/test_codegen_trim.py holds the census).
+static JJ_DEV void mont_xdbladd(const Fe& ox1, u32 sw, Fe& x2, Fe& z2, Fe& x3, Fe& z3) {
   typedef Fq F;
-  const Fe oa = F::opaque(F::carry(F::add(x2, z2)));
-  const Fe ob = F::opaque(F::sub(x2, z2));
+  const Fe s2 = F::opaque(F::add(x2, z2)), d2 = F::opaque(F::sub(x2, z2)), s3 = F::opaque(F::add(x3, z3)), d3 = F::opaque(F::sub(x3, z3));
+  const Fe oa = F::opaque(F::carry(F::opaque(F::select(s2, s3, sw))));
+  const Fe ob = F::opaque(F::select(d2, d3, sw));
+  const Fe da = F::mul_hidden(d3, s2), cb = F::mul_hidden(s3, d2);
   const Fe aa = F::sqr_hidden(oa), bb = F::sqr_hidden(ob);
-  const Fe da = F::mul_hidden(F::opaque(F::sub(x3, z3)), oa);
-  const Fe cb = F::mul_hidden(F::opaque(F::add(x3, z3)), ob);
   const Fe e = F::sub(aa, bb);
   const Fe w = F::add(aa, mont_a24(e));
   x3 = F::sqr(F::carry(F::add(da, cb)));
@@ -91,10 +97,7 @@ static JJ_DEV void varbase_mont(const Affine& P, const Fe& x1, const u32 (&k_in)
     u32 sw = (u32)((i32)g[7] >> 31);                  // all-ones iff bit_i != bit_(i+1)
     _Pragma("unroll") for (int q = 7; q >= 1; q--) g[q] = (g[q] << 1) | (g[q - 1] >> 31);
     g[0] <<= 1;
-    const Fe sx2 = F::select(x2, x3, sw), sx3 = F::select(x3, x2, sw);
-    const Fe sz2 = F::select(z2, z3, sw), sz3 = F::select(z3, z2, sw);
-    x2 = sx2; x3 = sx3; z2 = sz2; z3 = sz3;
-    mont_xdbladd(ox1, x2, z2, x3, z3);
+    mont_xdbladd(ox1, sw, x2, z2, x3, z3);
   }
   const u32 last = 0u - (k[0] & 1u);                  // the final swap: bit 0
   const Fe xq = F::select(x2, x3, last), zq = F::select(z2, z3, last);

@@ -394,17 +394,25 @@ def check_mont_ladder(verbose=True):
     acc = ONE
     for _ in range(3):
         acc = F.join(acc, F.mul(acc, den, "x1.prefix"))
-    chain = F.join(acc, F.mul(acc, acc, "x1.invert"))
+    # invert_divsteps: to_plain of the prefix product going in; coming out, sign(f) d regrouped into 29-bit limbs (limbs 0..7 masked, value
+    # in (-2p, 2p)) times R^2: a product like the power chain's (the chain stays modelled: Field::invert serves the other callers)
+    F.canon_ok(acc, "x1.invert_divsteps.to_plain")
+    dsx = V([0] * (NL - 1) + [-2 * Q >> TOP], [MASK] * (NL - 1) + [2 * Q >> TOP], -2 * Q, 2 * Q)
+    chain = F.join(acc, F.mul(dsx, F.const((MONT * MONT) % Q), "x1.invert_divsteps.R2"))
+    chain = F.join(chain, F.mul(acc, acc, "x1.invert"))
     chain = F.join(chain, F.mul(chain, chain, "x1.invert"))
     inv = F.join(chain, F.mul(chain, den, "x1.inv*d"))
     di = F.mul(inv, chain, "x1.inv*prefix")
     x1 = F.mul(F.carry(num), di, "x1")
-    # ladder state: (1 : 0), (x1 : 1), then products; the masked swap joins the classes
+    # ladder state: (1 : 0), (x1 : 1), then products; one class for all four coordinates
     st = F.join(F.join(ONE, ZERO), x1)
     for it in range(80):
-        a, b = F.carry(F.add(st, st), "lad.A"), F.sub(st, st, "lad.B")
+        # the state is not swapped: the doubling squares the selected sum (carried) and the selected difference, and the addition
+        # multiplies each difference by the other point's uncarried sum
+        s2, d2, s3, d3 = F.add(st, st, "lad.S2"), F.sub(st, st, "lad.D2"), F.add(st, st, "lad.S3"), F.sub(st, st, "lad.D3")
+        a, b = F.carry(F.select(s2, s3), "lad.A"), F.select(d2, d3)
         aa, bb = F.sqr(a, "lad.AA"), F.sqr(b, "lad.BB")
-        da, cb = F.mul(F.sub(st, st), a, "lad.DA"), F.mul(F.add(st, st), b, "lad.CB")
+        da, cb = F.mul(d3, s2, "lad.DA"), F.mul(s3, d2, "lad.CB")
         e = F.sub(aa, bb, "lad.E")
         w = F.add(aa, F.mul_a24(e), "lad.AA+a24E")
         outs = [F.sqr(F.carry(F.add(da, cb)), "lad.x3"), F.mul(x1, F.sqr(F.sub(da, cb), "lad.(DA-CB)^2"), "lad.z3"),
