@@ -693,16 +693,17 @@ __global__ void __launch_bounds__(256) k_varbase_mont_x1(size_t n, const void* p
     ext.put(2, i, Fq::mul(Fq::carry(num), di));
   }
 }
-// 3 waves per SIMD (<= 168 VGPRs): the ladder state is five field elements and the Gray-code register, no table
+// 3 waves per SIMD (<= 168 VGPRs): the ladder state is five field elements and the Gray-code register, no table.  The base point is loaded
+// (and x1 read again) after the ladder: neither is then live across the loop, which otherwise spills.
 __global__ void __launch_bounds__(256, 3) k_varbase_mont(size_t n, const void* scalars, const void* points, SoA ext) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   u32 k[8];
   load8(k, scalars, i);
+  Fe u, v, z, xq, zq, xp, zp;
+  const u32 last = varbase_mont_ladder(ext.get(2, i), k, xq, zq, xp, zp);
   const Affine P = load_affine(points, i);
-  const Fe x1 = ext.get(2, i);
-  Fe u, v, z;
-  varbase_mont(P, x1, k, u, v, z);
+  varbase_mont_recover(P, ext.get(2, i), last, xq, zq, xp, zp, u, v, z);
   ext.put(0, i, u); ext.put(1, i, v); ext.put(2, i, z);
 }
 #endif  // JJ_KERNELS_BATCH

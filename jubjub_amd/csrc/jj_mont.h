@@ -10,6 +10,10 @@
 // four, src/lib.rs:357-379), from (1 : 0) and (x1 : 1).  Per bit one masked select of the doubling's two inputs keyed on bit_i ^ bit_(i+1) -- the bits of the Gray
 // code k ^ (k >> 1), shifted out of eight registers -- then 4S + 5M and one multiplication by a24 (mont_a24: 9 + 9 multiply-adds and
 // a carry, no product).  No load, store, branch or address of the loop depends on the scalar.
+// The three sums of the step (x2 + z2, x3 + z3, DA + CB) are formed as x + z - q with q written in limbs near 2^29 (MontK::QBIAS): the
+// same residue with limbs centred on zero, so that they can be squared and multiplied without a carry step (mont_xdbladd).
+// The kernel runs the ladder (varbase_mont_ladder) before it loads the base point for the y-recovery (varbase_mont_recover): the
+// point's 18 registers are not live across the 252 iterations.
 // y-recovery: Okeya-Sakurai in the projective form of Costello-Smith ("Montgomery curves and their arithmetic", Algorithm 5), every
 // coordinate scaled by u instead of divided by y1 = x1/u, then (X : Y : Z) -> Edwards (X (X + Z) : Y (X - Z) : Y (X + Z)).
 // Exceptional inputs and results are masked, never branched on.  tests/mont_ladder_model.py is the same algorithm over integers.
@@ -19,7 +23,10 @@
 namespace jj {
 
 // Montgomery-form constants (R = 2^261): 2A, 2B, -1 (tests/test_mont_ladder_cpu.py recomputes them)
+// QBIAS: q itself (FqP::P) with its low eight limbs moved next to 2^29: from limb 0 up, a limb below 2^28 borrows 2^29 from the limb
+// above it.  sum QBIAS[i] 2^(29 i) = q and limbs 0..7 lie in [1.32 * 2^28, 2.76 * 2^28] (tests/test_mont_qbias_cpu.py recomputes it).
 struct MontK {
+  static constexpr u32 QBIAS[9] = {0x20000001u, 0x1ffffff7u, 0x1f96ffbfu, 0x1b4805ffu, 0x1d80553bu, 0x2c0404d0u, 0x1520cce6u, 0x2a6533afu, 0x0073eda6u};
   static constexpr u32 TWO_A[9] = {0x1fa7aa4fu, 0x02c2ad87u, 0x1bae6c40u, 0x0936fbd9u, 0x11652c16u, 0x13ce2c45u, 0x10c0760eu, 0x117bd639u, 0x006b8a64u};
   static constexpr u32 TWO_B[9] = {0x005856cdu, 0x1d3d4998u, 0x0fd54cbfu, 0x1aafac22u, 0x08f9624fu, 0x00a72b80u, 0x1fa2daa0u, 0x16c980a5u, 0x00301b3bu};
   static constexpr u32 NEG_ONE[9] = {0x00000047u, 0x1ffffdc8u, 0x02e0ee3fu, 0x10f9a9ffu, 0x0e97a399u, 0x151d55f1u, 0x1c18d42bu, 0x021155b7u, 0x0026e968u};
@@ -49,20 +56,40 @@ static JJ_DEV Fe mont_a24(const Fe& e) {
 // DA = (x3 - z3)(x2 + z2) and CB = (x3 + z3)(x2 - z2) and so leaves DA + CB and (DA - CB)^2 as they are: only the doubling reads the
 // swap bit, through two selects (the sum and the difference it squares).  (x2 : z2) <- 2 (sw ? (x3 : z3) : (x2 : z2)),
 // (x3 : z3) <- (x2 : z2) + (x3 : z3), difference (ox1 : 1); ox1 is already hidden (Field::opaque).  The state that leaves is the one a
-// masked swap of all four coordinates followed by RFC 7748's xDBLADD leaves.  Inputs and outputs are products ("N"); the two sums that
-// are squared get one carry step, DA and CB multiply a difference by an uncarried sum (tools/bounds_check.py mont_ladder).
-// The four sums are hidden once and multiplied as they are (mul_hidden), and the select is hidden before its carry: hipcc otherwise
-// re-expands it inside the carry's mask (v_and + two v_bitop3_b32 per limb), or spills (tests/test_codegen_trim.py holds the census).
-static JJ_DEV void mont_xdbladd(const Fe& ox1, u32 sw, Fe& x2, Fe& z2, Fe& x3, Fe& z3) {
+// masked swap of all four coordinates followed by RFC 7748's xDBLADD leaves.  Inputs and outputs are products ("N").
+// Bounds: a product has limbs 0..7 in [0, 2^29), so a plain sum of two has them in [0, 2^30) and the nine-term middle column of its
+// square could reach 9 * 2^60 > 2^63.  The sums are therefore biased by q: x + z - QBIAS is the same residue, its limbs 0..7 lie in
+// (-0.69 * 2^30, 0.67 * 2^30) and the columns of its square stay below 0.63 * 2^63 before the reduction terms; DA and CB multiply a
+// difference (limbs in (-2^29, 2^29)) by such a sum.  No carry step is left in the loop (tools/bounds_check.py check_mont_ladder;
+// tests/cpp/emu_mont_step.cpp plants the extreme limb patterns under the 128-bit shadow accumulators).
+// nqb = -QBIAS, limb by limb, held in scalar registers by the caller (mont_neg_qbias): a VOP3 instruction of gfx950 takes no 32-bit
+// literal, so for x + z - constant hipcc emits a literal v_subrev_u32 per limb next to the v_add_u32 (1 740 instructions per bit); from a
+// register the biased sum is one v_add3_u32 per limb, what the plain sum cost (1 711; profiles/r11_vb_bias_census.txt).
+// The four sums and differences are hidden once and multiplied as they are (mul_hidden), and so is the select: hipcc otherwise
+// re-expands it (v_and + two v_bitop3_b32 per limb), or spills (tests/test_codegen_trim.py, tests/test_codegen_bias.py hold the census).
+// -QBIAS limb by limb (two's complement), pinned to scalar registers on the device (see mont_xdbladd)
+static JJ_DEV Fe mont_neg_qbias() {
+  Fe r;
+  _Pragma("unroll") for (int i = 0; i < NL; i++) {
+    u32 c = 0u - MontK::QBIAS[i];
+#ifndef JJ_HOST_EMU
+    asm("" : "+s"(c));
+#endif
+    r.l[i] = c;
+  }
+  return r;
+}
+static JJ_DEV void mont_xdbladd(const Fe& ox1, const Fe& nqb, u32 sw, Fe& x2, Fe& z2, Fe& x3, Fe& z3) {
   typedef Fq F;
-  const Fe s2 = F::opaque(F::add(x2, z2)), d2 = F::opaque(F::sub(x2, z2)), s3 = F::opaque(F::add(x3, z3)), d3 = F::opaque(F::sub(x3, z3));
-  const Fe oa = F::opaque(F::carry(F::opaque(F::select(s2, s3, sw))));
+  const Fe s2 = F::opaque(F::add(F::add(x2, z2), nqb)), d2 = F::opaque(F::sub(x2, z2));
+  const Fe s3 = F::opaque(F::add(F::add(x3, z3), nqb)), d3 = F::opaque(F::sub(x3, z3));
+  const Fe oa = F::opaque(F::select(s2, s3, sw));
   const Fe ob = F::opaque(F::select(d2, d3, sw));
   const Fe da = F::mul_hidden(d3, s2), cb = F::mul_hidden(s3, d2);
   const Fe aa = F::sqr_hidden(oa), bb = F::sqr_hidden(ob);
   const Fe e = F::sub(aa, bb);
   const Fe w = F::add(aa, mont_a24(e));
-  x3 = F::sqr(F::carry(F::add(da, cb)));
+  x3 = F::sqr(F::add(F::add(da, cb), nqb));
   z3 = F::mul_hidden(ox1, F::opaque(F::sqr(F::sub(da, cb))));
   z2 = F::mul(e, w);
   x2 = F::mul(aa, bb);
@@ -78,9 +105,9 @@ static JJ_DEV Fe mont_x1_den(const Fe& v, Fe& num) {
 // masks of the canonical zero test of a product-form value (Field::is_zero_product, no product)
 static JJ_DEV u32 mont_zero_mask(const Fe& t) { return 0u - (u32)Fq::is_zero_product(t); }
 
-// k P for the affine point P = (u, v) (products, as load_affine gives them) and x1 = (1 + v)/(1 - v) (a product; any value when
-// v = 1).  k: 32 little-endian bytes as 8 words; bits 251..0 are used.  Result: a projective Edwards point (U : V : Z), products.
-static JJ_DEV void varbase_mont(const Affine& P, const Fe& x1, const u32 (&k_in)[8], Fe& ou, Fe& ov, Fe& oz) {
+// The ladder of k P: x1 = (1 + v)/(1 - v) of the base (a product; any value when v = 1), k: 32 little-endian bytes as 8 words, bits
+// 251..0 are used.  Leaves k P = (xq : zq) and (k + 1) P = (xp : zp), products, and returns the mask of the final swap (bit 0 of k).
+static JJ_DEV u32 varbase_mont_ladder(const Fe& x1, const u32 (&k_in)[8], Fe& xq, Fe& zq, Fe& xp, Fe& zp) {
   typedef Fq F;
   u32 k[8];
   _Pragma("unroll") for (int q = 0; q < 8; q++) k[q] = k_in[q];
@@ -91,17 +118,26 @@ static JJ_DEV void varbase_mont(const Affine& P, const Fe& x1, const u32 (&k_in)
   _Pragma("unroll") for (int q = 7; q >= 1; q--) g[q] = (g[q] << 4) | (g[q - 1] >> 28);
   g[0] <<= 4;
   const Fe ox1 = F::opaque(x1);
+  const Fe nqb = mont_neg_qbias();
   Fe x2 = F::one(), z2 = F::zero(), x3 = x1, z3 = F::one();
   #pragma unroll 1
   for (int i = 0; i < MONT_NBITS; i++) {
     u32 sw = (u32)((i32)g[7] >> 31);                  // all-ones iff bit_i != bit_(i+1)
     _Pragma("unroll") for (int q = 7; q >= 1; q--) g[q] = (g[q] << 1) | (g[q - 1] >> 31);
     g[0] <<= 1;
-    mont_xdbladd(ox1, sw, x2, z2, x3, z3);
+    mont_xdbladd(ox1, nqb, sw, x2, z2, x3, z3);
   }
   const u32 last = 0u - (k[0] & 1u);                  // the final swap: bit 0
-  const Fe xq = F::select(x2, x3, last), zq = F::select(z2, z3, last);
-  const Fe xp = F::select(x3, x2, last), zp = F::select(z3, z2, last);
+  xq = F::select(x2, x3, last); zq = F::select(z2, z3, last);
+  xp = F::select(x3, x2, last); zp = F::select(z3, z2, last);
+  return last;
+}
+
+// k P as a projective Edwards point (U : V : Z), products, from what the ladder left: P = (u, v) (products, as load_affine gives
+// them), its x1, last = the ladder's return value.
+static JJ_DEV void varbase_mont_recover(const Affine& P, const Fe& x1, u32 last, const Fe& xq, const Fe& zq, const Fe& xp, const Fe& zp,
+                                        Fe& ou, Fe& ov, Fe& oz) {
+  typedef Fq F;
 
   // y-recovery (Costello-Smith Algorithm 5), scaled by u
   const Fe v1 = F::mul(x1, zq);
@@ -128,6 +164,13 @@ static JJ_DEV void varbase_mont(const Affine& P, const Fe& x1, const u32 (&k_in)
   const u32 to_t2 = x10 & odd & ~ident;                                                                  // P = (0, -1), k odd
   U = F::select(U, zero, to_id | to_t2); V = F::select(F::select(V, one, to_id), negone, to_t2); W = F::select(W, one, to_id | to_t2);
   ou = U; ov = V; oz = W;
+}
+
+// ladder and y-recovery in one call (the host emulation; k_varbase_mont loads P between the two)
+static JJ_DEV void varbase_mont(const Affine& P, const Fe& x1, const u32 (&k_in)[8], Fe& ou, Fe& ov, Fe& oz) {
+  Fe xq, zq, xp, zp;
+  const u32 last = varbase_mont_ladder(x1, k_in, xq, zq, xp, zp);
+  varbase_mont_recover(P, x1, last, xq, zq, xp, zp, ou, ov, oz);
 }
 
 }  // namespace jj

@@ -381,6 +381,17 @@ def check_kernel_formulas(verbose=True):
         print("  kernel formulas (normalise, decode, sqrt, pairing, quad ops): ok")
 
 
+def qbias(p):
+    """MontK::QBIAS (jj_mont.h): the limbs of p with limbs 0..7 moved next to 2^29 -- from limb 0 up, a limb below 2^28 borrows 2^29 from
+    the limb above it"""
+    c = list(limbs(p))
+    for i in range(NL - 1):
+        if c[i] < 1 << 28:
+            c[i] += 1 << LB
+            c[i + 1] -= 1
+    return c
+
+
 def check_mont_ladder(verbose=True):
     """k_varbase_mont_x1 and k_varbase_mont (jj_mont.h): the batch inversion of 1 - v, the x-only ladder body iterated to a fixed point
     (every coordinate of the state is a product), the y-recovery, the map to Edwards and the masked outputs"""
@@ -406,16 +417,21 @@ def check_mont_ladder(verbose=True):
     x1 = F.mul(F.carry(num), di, "x1")
     # ladder state: (1 : 0), (x1 : 1), then products; one class for all four coordinates
     st = F.join(F.join(ONE, ZERO), x1)
+    # the three sums of the step are biased by q written in limbs near 2^29 (MontK::QBIAS): exact limbs, value q
+    QB = qbias(Q)
+    assert sum(x << (LB * i) for i, x in enumerate(QB)) == Q and all(1 << 28 <= x < 3 << 28 for x in QB[:-1])
+    qb = V(QB, QB, Q, Q)
     for it in range(80):
-        # the state is not swapped: the doubling squares the selected sum (carried) and the selected difference, and the addition
-        # multiplies each difference by the other point's uncarried sum
-        s2, d2, s3, d3 = F.add(st, st, "lad.S2"), F.sub(st, st, "lad.D2"), F.add(st, st, "lad.S3"), F.sub(st, st, "lad.D3")
-        a, b = F.carry(F.select(s2, s3), "lad.A"), F.select(d2, d3)
+        # the state is not swapped: the doubling squares the selected biased sum and the selected difference, and the addition
+        # multiplies each difference by the other point's biased sum; no carry step anywhere
+        s2, d2 = F.sub(F.add(st, st, "lad.S2"), qb, "lad.S2-q"), F.sub(st, st, "lad.D2")
+        s3, d3 = F.sub(F.add(st, st, "lad.S3"), qb, "lad.S3-q"), F.sub(st, st, "lad.D3")
+        a, b = F.select(s2, s3), F.select(d2, d3)
         aa, bb = F.sqr(a, "lad.AA"), F.sqr(b, "lad.BB")
         da, cb = F.mul(d3, s2, "lad.DA"), F.mul(s3, d2, "lad.CB")
         e = F.sub(aa, bb, "lad.E")
         w = F.add(aa, F.mul_a24(e), "lad.AA+a24E")
-        outs = [F.sqr(F.carry(F.add(da, cb)), "lad.x3"), F.mul(x1, F.sqr(F.sub(da, cb), "lad.(DA-CB)^2"), "lad.z3"),
+        outs = [F.sqr(F.sub(F.add(da, cb), qb, "lad.DA+CB-q"), "lad.x3"), F.mul(x1, F.sqr(F.sub(da, cb), "lad.(DA-CB)^2"), "lad.z3"),
                 F.mul(e, w, "lad.z2"), F.mul(aa, bb, "lad.x2")]
         nxt = st
         for o in outs:
