@@ -281,6 +281,33 @@ int jj_fixedbase_table_create(jj_ctx*, const void* base64, int window_bits /* 0 
 int jj_fixedbase_table_destroy(jj_ctx*, jj_table* t);
 int jj_fixedbase_mul(jj_ctx*, const jj_table* t, size_t n, const void* scalars32, void* out64);
 int jj_fixedbase_mul_compressed(jj_ctx*, const jj_table* t, size_t n, const void* scalars32, void* out32);
+/* One fixed and one variable term per unit: out[i] = to_affine(a[i] * G + b[i] * Q[i]), G the base of `t` (jj_fixedbase_table_create; every
+ * window_bits).  The shape of a Schnorr / RedJubjub check [s]G - [c]A (the caller negates A with jj_point_neg), of a re-randomised key
+ * ak + [alpha]G and of a Pedersen opening against one fixed generator.  _compressed returns to_bytes of the point: what a verifier compares
+ * with the signature's R.
+ * VARIABLE-TIME, for PUBLIC scalars only: digit-dependent addresses in both terms, whatever the table kind.
+ * Scalars are raw 32-byte patterns; only the low 252 bits are used.  They are integers, never reduced mod r, so the result is exact on the
+ * whole curve: cofactor components, the identity, (0, -1), scalars >= r.  Results are specified for on-curve points.  The Edwards law used is
+ * complete: Q = G, Q = -G, a G = -b Q, zero scalars and an identity Q take no special path.
+ * Every unit equals, byte for byte, jj_point_add(jj_fixedbase_mul(t, a), jj_varbase_mul(b, Q)) and jj_varbase_mul2_vartime(a, G broadcast, b, Q).
+ * Three routes, the same bytes from each, chosen by the table kind and n (no option picks one; vb_quad_max moves the boundary):
+ *   window_bits 8..16, n > vb_quad_max : ONE kernel, one unit per lane: the signed 5-bit ladder of jj_varbase_mul_vartime on (b, Q) -- 250
+ *       doublings, 51 additions, the lane's 17-entry table in device memory -- and then, in the same registers, ceil(253 / w) mixed additions of
+ *       entries gathered from G's table (w = 10: 26): G costs no table build per lane and no doubling;
+ *   window_bits 6, 7, n > vb_quad_max  : the ladder, then the table's own LDS kernel on the accumulator it left (two launches; the LDS kernels need
+ *       a whole CU's LDS and one workgroup per CU);
+ *   n <= vb_quad_max                   : the quad-of-lanes ladder, then the table's own kernel (the latency path).
+ * Pointers may be host or device, mixed freely.  n = 0 succeeds and touches nothing.  JJ_ERR_INVALID before any device work: a NULL context or
+ * table, a NULL array with n > 0, a table of another device (the message of jj_fixedbase_mul), a composite table from
+ * jj_fixedbase_composite_create (the message says so).  Context lock, stream rules, jj_profile_*, the result pool and jj_host_alloc buffers: as
+ * jj_varbase_mul2_vartime; all-host arrays of pipeline size go through the host-buffer pipeline in chunks (a, b and Q; the table stays resident).
+ * Out of scope: a third addend and cofactor clearing -- compose jj_point_add / jj_point_mul_by_cofactor.
+ * Measured on an MI355X (profiles/fixedvar_ab.txt, 2^20 units, device-resident, ms per call): table 13 is the fastest gathered width (13.99; 10: 14.19,
+ * 8: 14.43; the default LDS table: 15.09) against 15.43 for the three composed calls and 17.45 for jj_varbase_mul2_vartime with G broadcast, spreads
+ * <= 0.18; the fixed term costs 6.6 % (w = 13) to 9.9 % (w = 8) over jj_varbase_mul_vartime alone (13.13).  Recommended: window_bits 13 (a 10.5 MB
+ * table), or 10 (3.4 MB) within 1.5 % of it. */
+int jj_fixedvar_mul_vartime(jj_ctx*, const jj_table* t, size_t n, const void* a32, const void* b32, const void* q64, void* out64);
+int jj_fixedvar_mul_vartime_compressed(jj_ctx*, const jj_table* t, size_t n, const void* a32, const void* b32, const void* q64, void* out32);
 /* Sums over several fixed bases (the primitive is AffineNielsPoint::multiply_bits, src/lib.rs:297-301):
  *   out[i] = sum_{j < nbases} tables[j] * scalars32[j * n + i]      (base-major scalar array, nbases * n * 32 bytes)
  * e.g. value commitments v*G_v + r*G_r or windowed Pedersen sums.  One pass per base; the accumulator stays in

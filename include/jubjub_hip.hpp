@@ -474,6 +474,15 @@ inline AffineBatch multiply2_scalars(const Context& c, const AffineBatch& p, con
   c.check(jj_varbase_mul2_scalars(c.raw(), p.len(), ab, p.coords().data(), q.coords().data(), out.data()));
   return AffineBatch(c, std::move(out));
 }
+// g * a[i] + q[i] * b[i], g the base of a FixedBase (jj_fixedvar_mul_vartime): variable-time, for PUBLIC scalars only; the same points as
+// g * a, multiply_vartime(q, b) and a sum
+inline AffineBatch multiply_fixed_add_vartime(const FixedBase& g, const FrBatch& a, const AffineBatch& q, const FrBatch& b) {
+  if (a.len() != b.len() || q.len() != b.len()) throw Error(JJ_ERR_INVALID, "length mismatch");
+  const Context& c = g.context();
+  std::vector<Bytes64> out(q.len());
+  c.check(jj_fixedvar_mul_vartime(c.raw(), g.raw(), q.len(), a.to_bytes().data(), b.to_bytes().data(), q.coords().data(), out.data()));
+  return AffineBatch(c, std::move(out));
+}
 // several fixed bases with short scalars through one LDS table set, one pass (sums of multiply_bits, lib.rs:297-301)
 class CompositeBase {
  public:

@@ -46,6 +46,8 @@ _SIGS.update({
     "jj_fixedbase_mul_compressed": [_vp, _sz, _vp, _vp],
     "jj_fixedbase_table_destroy": [_vp],
     "jj_fixedbase_mul": [_vp, _sz, _vp, _vp],
+    "jj_fixedvar_mul_vartime": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "jj_fixedvar_mul_vartime_compressed": [_vp, _sz, _vp, _vp, _vp, _vp],
     "jj_fixedbase_multi_mul": [_vp, C.c_int, _sz, _vp, _vp],
     "jj_fixedbase_composite_create": [C.c_int, _vp, C.POINTER(C.c_int), C.POINTER(_vp)],
     "jj_fixedbase_composite_mul": [_vp, _sz, _vp, _vp],

@@ -651,6 +651,75 @@ JJ_API int jj_fixedbase_composite_mul(jj_ctx* c, const jj_table* t, size_t n, co
 }
 JJ_API int jj_fixedbase_mul_compressed(jj_ctx* c, const jj_table* t, size_t n, const void* scalars, void* out32) { return fixedbase_api(c, t, n, scalars, out32, 1); }
 
+// ---- one fixed and one variable term per unit: out[i] = a[i] G + b[i] Q[i], G the base of `t`.  VARIABLE-TIME like the _vartime entry points of the
+// var-base ladder.  Three routes, the same bytes from each: a gathered table (window_bits 8..16) above vb_quad_max units runs both terms in one
+// accumulator (k_varbase_fixed, jj_fixedvar.h); an LDS table (6, 7) runs k_varbase<true> and then its own kernel on the five coordinates left in
+// `ext` (chain = 1: the LDS kernels need a whole CU's LDS and one workgroup per CU, the ladder a table slot per lane and two waves per SIMD); up to
+// vb_quad_max units every table kind runs the quad ladder (k_varbase_quad<true>) and then its own kernel.  `ext` holds five coordinates.
+// JJ_FIXEDVAR_PROBE_SPLIT (experiments only, the same results): gathered tables take the two launches of the LDS tables -- k_varbase<true>, then
+// k_fixedbase_gather with chain = 1 -- which is what the fused kernel has to beat (tools/fixedvar_ab.py, profiles/fixedvar_ab.txt)
+#if defined(JJ_FIXEDVAR_PROBE_SPLIT) && !defined(JJ_EXPERIMENTS)
+#error "JJ_FIXEDVAR_PROBE_SPLIT needs -DJJ_EXPERIMENTS: the shipped library is built with the defaults"
+#endif
+#ifdef JJ_FIXEDVAR_PROBE_SPLIT
+constexpr bool FIXEDVAR_FUSED = false;
+#else
+constexpr bool FIXEDVAR_FUSED = true;
+#endif
+static int fixedvar_to_ext(jj_ctx* c, const jj_table* t, size_t n, const void* da, const void* db, const void* dq, SoA ext) {
+  if (n <= (size_t)c->vb_quad_max || t->window_bits < 8 || !FIXEDVAR_FUSED) {
+    int rc = varbase_to_ext(c, n, db, dq, ext, true);
+    if (rc) return rc;
+    return fixedbase_launch(c, t, n, da, ext, /*chain=*/1);
+  }
+  unsigned blocks; size_t threads;
+  varbase_geometry(c, n, &blocks, &threads);
+  int rc = ensure(c, c->ws->tables, threads * (size_t)FixedVar<VB_W>::LANE_WORDS * 4); if (rc) return rc;
+  if ((rc = ensure(c, c->ws->cursor, 64))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->ws->cursor.p, 0, 8, c->stream));          // the waves' work cursor
+  hipLaunchKernelGGL(k_varbase_fixed, dim3(blocks), dim3(256), 0, c->stream, n, da, db, dq, (const u32*)t->dev, t->fp, (u32*)c->ws->tables.p, ext, (unsigned long long*)c->ws->cursor.p);
+  return JJ_OK;
+}
+static int fixedvar_api(jj_ctx* c, const jj_table* t, size_t n, const void* a, const void* b, const void* q, void* out, int mode) {
+  if (!c || !t) return JJ_ERR_INVALID;
+  if (n && (!a || !b || !q || !out)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_fixedvar_mul_vartime needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
+  if (const size_t ch = pipe_chunk_for(c, n, 18); ch && all_host({a, b, q, out})) {
+    const HostIn in[3] = {{a, 32}, {b, 32}, {q, 64}};      // the table stays resident
+    const HostOut ho[1] = {{out, (size_t)(mode ? 32 : 64)}};
+    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
+      int rc2;
+      if ((rc2 = ensure_ext(c, cn, 5))) return rc2;
+      SoA ext = soa_of(c->ws->ext, cn);
+      if ((rc2 = fixedvar_to_ext(c, t, cn, di[0], di[1], di[2], ext))) return rc2;
+      if ((rc2 = pipe_to_tail(c))) return rc2;
+      return normalize_launch(c, cn, ext, dout[0], mode);
+    });
+    if (prc <= 0) return prc;      // +1: buffers could not be page-locked -> plain staging below
+  }
+  const void *da, *db, *dq; int rc; OutRef o;
+  if ((rc = stage_in(c, 0, a, 32 * n, &da))) return rc;
+  if ((rc = stage_in(c, 2, b, 32 * n, &db))) return rc;
+  if ((rc = stage_in(c, 3, q, 64 * n, &dq))) return rc;
+  if ((rc = stage_out(c, c->out[0], out, (mode ? 32 : 64) * n, &o))) return rc;
+  if ((rc = ensure_ext(c, n, 5))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  if (n) {
+    prof_mark(c, 0);
+    if ((rc = fixedvar_to_ext(c, t, n, da, db, dq, ext))) return rc;
+    prof_mark(c, 1);
+    if ((rc = normalize_launch(c, n, ext, o.dev, mode))) return rc;
+    prof_mark(c, 2);
+  }
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
+JJ_API int jj_fixedvar_mul_vartime(jj_ctx* c, const jj_table* t, size_t n, const void* a32, const void* b32, const void* q64, void* out64) { return fixedvar_api(c, t, n, a32, b32, q64, out64, 0); }
+JJ_API int jj_fixedvar_mul_vartime_compressed(jj_ctx* c, const jj_table* t, size_t n, const void* a32, const void* b32, const void* q64, void* out32) { return fixedvar_api(c, t, n, a32, b32, q64, out32, 1); }
+
 // ---------------------------------------------------------------------------------------------------- sums / MSM
 // folds a 5-coordinate SoA of n extended points down to one, result left in (U,V,Z) coords of the returned SoA
 static int sum_reduce(jj_ctx* c, size_t n, DevBuf* a, DevBuf* b, SoA* result) {

@@ -1077,6 +1077,29 @@ __global__ void __launch_bounds__(256) k_fixedbase_gather(size_t n, const void* 
   }
 }
 #endif  // JJ_KERNELS_BATCH
+// One fixed and one variable term per unit, a G + b Q, in one accumulator (jj_fixedvar.h): k_varbase's persistent grid, cursor and lane
+// slot for Q's table, then the walk of k_fixedbase_gather over G's table (window_bits 8..16) without leaving the registers.
+}  // namespace jj
+#include "jj_fixedvar.h"
+namespace jj {
+#ifdef JJ_KERNELS_BATCH
+__global__ void __launch_bounds__(256, JJ_VB_MINWAVES) k_varbase_fixed(size_t n, const void* a, const void* b, const void* q, const u32* table, FbParams fp, u32* tables, SoA ext, unsigned long long* cursor) {
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u32* slot = tables + gtid * (size_t)FixedVar<VB_W>::LANE_WORDS;
+  size_t i;
+  #pragma unroll 1
+  while (next_wave_units(cursor, n, i)) {
+    if (i < n) {                                           // ragged last wave: as k_varbase
+      u32 ka[8], kb[8];
+      load8(ka, a, i);
+      load8(kb, b, i);
+      const Affine Q = load_affine(q, i);
+      const Ext r = FixedVar<VB_W>::mul_add(table, fp, ka, Q, kb, slot);
+      ext.put(0, i, r.u); ext.put(1, i, r.v); ext.put(2, i, r.z);
+    }
+  }
+}
+#endif  // JJ_KERNELS_BATCH
 // affine points (64 B canonical) -> table entries (AffineNiels limbs, 112 B)
 #ifdef JJ_KERNELS_BATCH
 __global__ void __launch_bounds__(256) k_affine_to_table(size_t n, const void* pts, u32* table, int stride) {

@@ -501,6 +501,15 @@ class Engine:
     def fixedbase_mul(self, table, scalars, out=None):
         return self._call("jj_fixedbase_mul", [scalars], [32], [64], extra_before=(table._h,), out=out)
 
+    def fixedvar_mul_vartime(self, table, a, b, q, out=None):
+        """G * a[i] + q[i] * b[i] for PUBLIC scalars, G the base of `table` (fixedbase_table, every window_bits): byte for byte
+        point_add(fixedbase_mul(table, a), varbase_mul(b, q)).  A gathered table (window_bits 8..16) runs both terms in one kernel
+        (jj_fixedvar_mul_vartime); digit-dependent addresses in both terms"""
+        return self._call("jj_fixedvar_mul_vartime", [a, b, q], [32, 32, 64], [64], extra_before=(table._h,), out=out)
+
+    def fixedvar_mul_vartime_compressed(self, table, a, b, q, out=None):
+        return self._call("jj_fixedvar_mul_vartime_compressed", [a, b, q], [32, 32, 64], [32], extra_before=(table._h,), out=out)
+
     def fixedbase_multi_mul(self, tables, scalars):
         """out[i] = sum_j tables[j] * scalars[j][i]; scalars: (len(tables), n, 32) bytes, base-major."""
         nb = len(tables)

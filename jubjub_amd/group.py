@@ -197,6 +197,16 @@ class Points:
             raise ValueError("length mismatch")
         return Points(self.engine, self.engine.varbase_mul2_vartime(kb, self.data, lb, other.data))
 
+    def mul_add_fixed_vartime(self, l, table, k):
+        """self * l + G * k, unit by unit, for PUBLIC scalars l, k (Fr batches or raw 32-byte rows), G the base of `table` (a FixedBase or an
+        engine's fixedbase_table): the variable term's ladder and the table's entries in one accumulator (Engine.fixedvar_mul_vartime)
+        instead of a fixed-base product, a variable-base product and a sum; the same points"""
+        lb = _as_rows(l.to_bytes() if hasattr(l, "to_bytes") else l, 32)
+        kb = _as_rows(k.to_bytes() if hasattr(k, "to_bytes") else k, 32)
+        if not (kb.shape[0] == lb.shape[0] == len(self)):
+            raise ValueError("length mismatch")
+        return Points(self.engine, self.engine.fixedvar_mul_vartime(getattr(table, "table", table), kb, lb, self.data))
+
     def sum(self):                                          # Sum (src/lib.rs:183-193)
         return Points(self.engine, self.engine.point_sum(self.data))
 

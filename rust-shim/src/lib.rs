@@ -226,6 +226,16 @@ impl Gpu {
         out.chunks_exact(64).map(get_point).collect()
     }
 
+    /// `g * a[i] + q[i] * b[i]` for PUBLIC scalars, `g` the base of a `FixedBase` (`[s]G - [c]A` of a Schnorr / RedJubjub check with `A` negated
+    /// by the caller) (`jj_fixedvar_mul_vartime`): the same points as `FixedBase::mul_batch`, `multiply_batch_vartime` and a sum, variable-time.
+    pub fn fixedvar_mul_vartime(&self, g: &FixedBase, a: &[Fr], b: &[Fr], q: &[AffinePoint]) -> Vec<AffinePoint> {
+        assert!(a.len() == b.len() && b.len() == q.len());
+        let (n, sa, sb, pq) = (a.len(), put_scalars(a), put_scalars(b), put_points(q));
+        let mut out = vec![0u8; 64 * n];
+        assert_eq!(unsafe { jj_fixedvar_mul_vartime(self.0, g.t, n, sa.as_ptr() as _, sb.as_ptr() as _, pq.as_ptr() as _, out.as_mut_ptr() as _) }, 0);
+        out.chunks_exact(64).map(get_point).collect()
+    }
+
     /// `is_torsion_free` (src/lib.rs:709-711) for a whole vector.
     pub fn is_torsion_free_batch(&self, points: &[AffinePoint]) -> Vec<bool> {
         let (n, p) = (points.len(), put_points(points));
