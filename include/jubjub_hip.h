@@ -23,6 +23,18 @@
  * jj_multi_* below drives several devices of one node from one process.
  *
  * Every function returns 0 on success or a negative jj_status.
+ *
+ * BUFFERS -- the contract of every batch entry point below (enforced byte for byte by tests/test_gpu_buffers.py and, for the host-only
+ * functions, tests/test_buffer_cases_cpu.py; the table of entry points is tests/buffer_cases.py):
+ *   - an entry point writes exactly rows x width bytes of each output array (n x 32 / 64 / 96 / 160 / 256 bytes, n bytes of `ok` or of a
+ *     predicate, 4 n bytes of `attempts`; one row where the result is one point or one record): not a byte in front of the array, not a byte
+ *     behind it, whatever n is -- also when n is no multiple of a quad, a wave or a workgroup -- and every row of it, the rows whose `ok` is 0
+ *     (zeroed) and the empty segments of jj_msm_ragged (the identity) included.  A writer with a `cap` writes at most cap entries;
+ *   - it reads its input arrays and never writes them: no input serves as scratch;
+ *   - a device pointer needs 16-byte alignment and nothing more (jj_status JJ_ERR_INVALID otherwise); a host pointer needs none.  Arrays of one
+ *     call may be aligned differently and may lie directly next to each other;
+ *   - n = 0 (B = 0, S = 0) succeeds and touches nothing, but for the one result row of jj_point_sum and the jj_msm family (the identity).
+ * In-place calls -- an output array that overlaps an input array of the same call -- are NOT promised by any entry point: hand over disjoint arrays.
  */
 #ifndef JUBJUB_HIP_H
 #define JUBJUB_HIP_H
