@@ -23,25 +23,51 @@ int jj_batch_init(jj_ctx* c) {
   return JJ_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------- the front end
+// What every batch entry point does around its launches: resolve the per-unit arrays of a call of n units, run
+// `body(cn, din, dout, staged)`, deliver the results.  The body enqueues the kernels of cn units on c->stream; din[k] / dout[k] are device
+// pointers in the order of `in` / `out`, null for an array of 0 bytes per unit.
+//   ch != 0 (the entry point's own pipe_chunk_for; 0: never) and every array a host pointer: the host-buffer pipeline runs the body once
+//   per chunk, with staged = false.
+//   Otherwise, and when the pipeline could not page-lock the caller's arrays: every input is staged, then every output (a NULL array or a
+//   misaligned device pointer is refused there, before any launch), the body runs once with cn = n and staged = true -- not at all when
+//   n = 0 -- and the results are copied out, with the synchronisation that needs.
+// The caller has checked its other arguments and holds the context (JJ_ENTER).  A new entry point supplies the descriptors and a body.
+template <class Body>
+static int run_batch(jj_ctx* c, size_t n, std::initializer_list<ArgIn> in, std::initializer_list<ArgOut> out, size_t ch, size_t quantum, Body body) {
+  int rc;
+  if (in.size() > (size_t)ARGS_IN_MAX || out.size() > (size_t)ARGS_OUT_MAX) { c->err = "run_batch: more arrays than ARGS_IN_MAX / ARGS_OUT_MAX"; return JJ_ERR_INVALID; }
+  if (ch) {
+    bool all_host = true;
+    for (const ArgIn& a : in) all_host = all_host && a.p && !is_device_ptr(a.p);
+    for (const ArgOut& a : out) all_host = all_host && a.p && !is_device_ptr(a.p);
+    if (all_host) {
+      rc = run_pipelined(c, n, ch, in.begin(), (int)in.size(), out.begin(), (int)out.size(),
+                         [&](size_t cn, const void* const* din, void* const* dout) -> int { return body(cn, din, dout, false); }, quantum);
+      if (rc <= 0) return rc;      // +1: buffers could not be page-locked -> plain staging below
+    }
+  }
+  const void* din[ARGS_IN_MAX]; OutRef o[ARGS_OUT_MAX]; void* dout[ARGS_OUT_MAX];
+  int nin = 0, nout = 0;
+  for (const ArgIn& a : in) if ((rc = stage_in(c, a.slot, a.p, a.elem * n, &din[nin++]))) return rc;
+  for (const ArgOut& a : out) { if ((rc = stage_out(c, *a.buf, a.p, a.elem * n, &o[nout]))) return rc; dout[nout] = o[nout].dev; nout++; }
+  if (n && (rc = body(n, din, dout, true))) return rc;
+  bool sync = false;
+  for (int k = 0; k < nout; k++) if ((rc = finish_out(c, o[k], &sync))) return rc;
+  return finish(c, sync);
+}
+
 // ---------------------------------------------------------------------------------------------------- fields
 template <class P, int OP>
 static int field_op(jj_ctx* c, size_t n, const void* a, const void* b, void* out, uint8_t* ok, bool want_ok) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const size_t in_bytes = (OP == OP_FROM_WIDE ? 64 : 32) * n;
-  const void *da = nullptr, *db = nullptr;
-  int rc;
-  if ((rc = stage_in(c, 0, a, in_bytes, &da))) return rc;
   const bool binary = (OP == OP_ADD || OP == OP_SUB || OP == OP_MUL);
-  if (binary && (rc = stage_in(c, 1, b, 32 * n, &db))) return rc;
-  OutRef o, ok_o; ok_o.host = false; ok_o.dev = nullptr;
-  if ((rc = stage_out(c, c->out[0], out, 32 * n, &o))) return rc;
-  if (want_ok && (rc = stage_out(c, c->okb, ok, n, &ok_o))) return rc;
-  if (n) hipLaunchKernelGGL((k_field_op<P, OP>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, da, db, o.dev, (uint8_t*)ok_o.dev, c->sqrt_tables);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  if (want_ok && (rc = finish_out(c, ok_o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{a, OP == OP_FROM_WIDE ? 64 : 32, 0}, {b, (size_t)(binary ? 32 : 0), 1}}, {{out, 32, &c->out[0]}, {ok, (size_t)(want_ok ? 1 : 0), &c->okb}}, 0, 0,
+                   [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    hipLaunchKernelGGL((k_field_op<P, OP>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], din[1], dout[0], (uint8_t*)dout[1], c->sqrt_tables);
+    return JJ_OK;
+  });
 }
 #define FIELD_BIN(name, P, OP) JJ_API int name(jj_ctx* c, size_t n, const void* a, const void* b, void* out) { return field_op<P, OP>(c, n, a, b, out, nullptr, false); }
 #define FIELD_UN(name, P, OP) JJ_API int name(jj_ctx* c, size_t n, const void* a, void* out) { return field_op<P, OP>(c, n, a, nullptr, out, nullptr, false); }
@@ -59,14 +85,10 @@ template <class P>
 static int field_pow(jj_ctx* c, size_t n, const void* a, const void* e, void* out) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void *da, *de; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, a, 32 * n, &da))) return rc;
-  if ((rc = stage_in(c, 1, e, 32 * n, &de))) return rc;
-  if ((rc = stage_out(c, c->out[0], out, 32 * n, &o))) return rc;
-  if (n) hipLaunchKernelGGL((k_field_pow<P>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, da, de, o.dev);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{a, 32, 0}, {e, 32, 1}}, {{out, 32, &c->out[0]}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    hipLaunchKernelGGL((k_field_pow<P>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], din[1], dout[0]);
+    return JJ_OK;
+  });
 }
 JJ_API int jj_fq_pow(jj_ctx* c, size_t n, const void* a, const void* exp32, void* out) { return field_pow<FqP>(c, n, a, exp32, out); }
 JJ_API int jj_fr_pow(jj_ctx* c, size_t n, const void* a, const void* exp32, void* out) { return field_pow<FrP>(c, n, a, exp32, out); }
@@ -75,13 +97,10 @@ template <class P>
 static int field_to_bits(jj_ctx* c, size_t n, const void* a, void* out256) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void* da; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, a, 32 * n, &da))) return rc;
-  if ((rc = stage_out(c, c->out[0], out256, 256 * n, &o))) return rc;
-  if (n) hipLaunchKernelGGL((k_field_to_bits<P>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, da, o.dev);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{a, 32, 0}}, {{out256, 256, &c->out[0]}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    hipLaunchKernelGGL((k_field_to_bits<P>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], dout[0]);
+    return JJ_OK;
+  });
 }
 JJ_API int jj_fq_to_le_bits(jj_ctx* c, size_t n, const void* a, void* out256) { return field_to_bits<FqP>(c, n, a, out256); }
 JJ_API int jj_fr_to_le_bits(jj_ctx* c, size_t n, const void* a, void* out256) { return field_to_bits<FrP>(c, n, a, out256); }
@@ -110,26 +129,38 @@ static int normalize_launch(jj_ctx* c, size_t n, SoA ext, void* dout, int mode) 
   return JJ_OK;
 }
 
+// The scalar-multiplication family on top of run_batch: `to_ext(cn, din, ext)` leaves cn extended points of `coords` coordinates in c->ws->ext,
+// the normaliser turns them into the one output (mode 0: affine, 64 bytes; 1: compressed, 32).  A staged call records the profile's three marks
+// around the two (bench.py's kernel_ms); in the pipeline the normaliser moves to the tail stream (stream mode 3) and nothing is recorded.
+template <class ToExt>
+static int run_to_points(jj_ctx* c, size_t n, std::initializer_list<ArgIn> in, void* out, int mode, int coords, size_t ch, size_t quantum, ToExt to_ext) {
+  return run_batch(c, n, in, {{out, (size_t)(mode ? 32 : 64), &c->out[0]}}, ch, quantum, [&](size_t cn, const void* const* din, void* const* dout, bool staged) -> int {
+    int rc;
+    if ((rc = ensure_ext(c, cn, coords))) return rc;
+    SoA ext = soa_of(c->ws->ext, cn);
+    if (staged) prof_mark(c, 0);
+    if ((rc = to_ext(cn, din, ext))) return rc;
+    if (staged) prof_mark(c, 1);
+    else if ((rc = pipe_to_tail(c))) return rc;
+    if ((rc = normalize_launch(c, cn, ext, dout[0], mode))) return rc;
+    if (staged) prof_mark(c, 2);
+    return JJ_OK;
+  });
+}
+
 // ---------------------------------------------------------------------------------------------------- point ops
 template <int OP>
 static int point_op(jj_ctx* c, size_t n, const void* p, const void* q, void* out, size_t out_elem) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void *dp = nullptr, *dq = nullptr;
-  int rc;
-  if ((rc = stage_in(c, 0, p, 64 * n, &dp))) return rc;
-  if ((OP == PT_ADD || OP == PT_SUB) && (rc = stage_in(c, 1, q, 64 * n, &dq))) return rc;
-  OutRef o;
-  if ((rc = stage_out(c, c->out[0], out, out_elem * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    hipLaunchKernelGGL((k_point_op<OP>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dp, dq, ext, o.dev);
-    if (OP <= PT_COFACTOR && (rc = normalize_launch(c, n, ext, o.dev, 0))) return rc;
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{p, 64, 0}, {q, (OP == PT_ADD || OP == PT_SUB) ? 64 : 0, 1}}, {{out, out_elem, &c->out[0]}}, 0, 0,
+                   [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    int rc;
+    if ((rc = ensure_ext(c, n, 3))) return rc;
+    SoA ext = soa_of(c->ws->ext, n);
+    hipLaunchKernelGGL((k_point_op<OP>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], din[1], ext, dout[0]);
+    return OP <= PT_COFACTOR ? normalize_launch(c, n, ext, dout[0], 0) : JJ_OK;
+  });
 }
 JJ_API int jj_point_double(jj_ctx* c, size_t n, const void* p, void* out) { return point_op<PT_DOUBLE>(c, n, p, nullptr, out, 64); }
 JJ_API int jj_point_add(jj_ctx* c, size_t n, const void* p, const void* q, void* out) { return point_op<PT_ADD>(c, n, p, q, out, 64); }
@@ -142,12 +173,17 @@ JJ_API int jj_is_small_order(jj_ctx* c, size_t n, const void* p, uint8_t* out) {
 JJ_API int jj_is_on_curve(jj_ctx* c, size_t n, const void* p, uint8_t* out) { return point_op<PT_IS_ON_CURVE>(c, n, p, nullptr, out, 1); }
 
 // ---------------------------------------------------------------------------------------------------- var-base
-// launch geometry of the windowed ladder: persistent grid, one 2448-byte table slot (17 entries x 144 B) per lane
-static void varbase_geometry(jj_ctx* c, size_t n, unsigned* blocks, size_t* threads) {
+// launch geometry of the windowed ladders: persistent grid (blocks of 256 lanes), one table slot of `lane_words` words per lane
+// (k_varbase: 17 entries x 144 B = 2448 bytes) and the waves' work cursor, zeroed on c->stream ahead of the ladder
+static int ladder_workspace(jj_ctx* c, size_t n, size_t lane_words, unsigned* blocks) {
   const size_t max_threads = (size_t)c->cus * 256 * c->vb_blocks_per_cu;   // k blocks of 256 per CU = k waves / SIMD
-  size_t t = std::min(max_threads, ((n + 255) / 256) * 256);
-  if (t == 0) t = 256;
-  *blocks = (unsigned)(t / 256); *threads = t;
+  size_t threads = std::min(max_threads, ((n + 255) / 256) * 256);
+  if (threads == 0) threads = 256;
+  *blocks = (unsigned)(threads / 256);
+  int rc = ensure(c, c->ws->tables, threads * lane_words * 4); if (rc) return rc;
+  if ((rc = ensure(c, c->ws->cursor, 64))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->ws->cursor.p, 0, 8, c->stream));
+  return JJ_OK;
 }
 // ct: the ladder with the reference's timing discipline (no scalar-dependent address or branch): k_varbase_mont / _ct3 / _ct / _ct_quad; otherwise the
 // per-lane window table in memory (k_varbase / k_varbase_quad: digit-dependent addresses)
@@ -168,11 +204,8 @@ static int varbase_to_ext(jj_ctx* c, size_t n, const void* ds, const void* dp, S
     else hipLaunchKernelGGL(k_varbase_quad<false>, dim3(blocks_for(4 * n)), dim3(256), 0, c->stream, n, ds, dp, (u32*)c->ws->tables.p, ext);
     return JJ_OK;
   }
-  unsigned blocks; size_t threads;
-  varbase_geometry(c, n, &blocks, &threads);
-  int rc = ensure(c, c->ws->tables, threads * (size_t)(VB_SLOTS * ENIELS_WORDS) * 4); if (rc) return rc;
-  if ((rc = ensure(c, c->ws->cursor, 64))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->ws->cursor.p, 0, 8, c->stream));          // the waves' work cursor
+  unsigned blocks;
+  int rc = ladder_workspace(c, n, VB_SLOTS * ENIELS_WORDS, &blocks); if (rc) return rc;
   if (shared_scalar) hipLaunchKernelGGL((k_varbase<false, true>), dim3(blocks), dim3(256), 0, c->stream, n, ds, dp, (u32*)c->ws->tables.p, ext, (unsigned long long*)c->ws->cursor.p);
   else if (five) hipLaunchKernelGGL((k_varbase<true, false>), dim3(blocks), dim3(256), 0, c->stream, n, ds, dp, (u32*)c->ws->tables.p, ext, (unsigned long long*)c->ws->cursor.p);
   else hipLaunchKernelGGL((k_varbase<false, false>), dim3(blocks), dim3(256), 0, c->stream, n, ds, dp, (u32*)c->ws->tables.p, ext, (unsigned long long*)c->ws->cursor.p);
@@ -181,35 +214,9 @@ static int varbase_to_ext(jj_ctx* c, size_t n, const void* ds, const void* dp, S
 static int varbase_api(jj_ctx* c, size_t n, const void* scalars, const void* points, void* out, int mode, bool ct) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  if (const size_t ch = pipe_chunk_for(c, n, 18); ch && all_host({scalars, points, out})) {
-    const HostIn in[2] = {{scalars, 32}, {points, 64}};
-    const HostOut ho[1] = {{out, (size_t)(mode ? 32 : 64)}};
-    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
-      int rc2;
-      if ((rc2 = ensure_ext(c, cn, 3))) return rc2;
-      SoA ext = soa_of(c->ws->ext, cn);
-      if ((rc2 = varbase_to_ext(c, cn, di[0], di[1], ext, false, false, ct))) return rc2;
-      if ((rc2 = pipe_to_tail(c))) return rc2;
-      return normalize_launch(c, cn, ext, dout[0], mode);
-    });
-    if (prc <= 0) return prc;      // +1: buffers could not be page-locked -> plain staging below
-  }
-  const void *ds, *dp; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, scalars, 32 * n, &ds))) return rc;
-  if ((rc = stage_in(c, 1, points, 64 * n, &dp))) return rc;
-  if ((rc = stage_out(c, c->out[0], out, (mode ? 32 : 64) * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    prof_mark(c, 0);
-    if ((rc = varbase_to_ext(c, n, ds, dp, ext, false, false, ct))) return rc;
-    prof_mark(c, 1);
-    if ((rc = normalize_launch(c, n, ext, o.dev, mode))) return rc;
-    prof_mark(c, 2);
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_to_points(c, n, {{scalars, 32, 0}, {points, 64, 1}}, out, mode, 3, pipe_chunk_for(c, n, 18), 0, [&](size_t cn, const void* const* din, SoA ext) -> int {
+    return varbase_to_ext(c, cn, din[0], din[1], ext, false, false, ct);
+  });
 }
 // ExtendedPoint * Fr (reference src/lib.rs:873-879 -> 357-379): the reference's ladder is constant-time (conditional_select, 334-343), and so is
 // the default here: the x-only Montgomery ladder (k_varbase_mont after k_varbase_mont_x1; vb_ct_window = 3 / 2: the signed-window Edwards
@@ -226,35 +233,27 @@ JJ_API int jj_varbase_mul_vartime_compressed(jj_ctx* c, size_t n, const void* sc
 JJ_API int jj_varbase_mul_scalar(jj_ctx* c, size_t n, const void* scalar32, const void* points, void* out) {
   if (!c || !scalar32) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void* dp; int rc; OutRef o;
-  if ((rc = stage_in(c, 1, points, 64 * n, &dp))) return rc;
-  if ((rc = stage_out(c, c->out[0], out, 64 * n, &o))) return rc;
-  if ((rc = ensure(c, c->ws_tmp[1], 32))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->ws_tmp[1].p, scalar32, 32, is_device_ptr(scalar32) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
+  return run_batch(c, n, {{points, 64, 1}}, {{out, 64, &c->out[0]}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    int rc;
+    if ((rc = ensure(c, c->ws_tmp[1], 32))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->ws_tmp[1].p, scalar32, 32, is_device_ptr(scalar32) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if ((rc = ensure_ext(c, n, 3))) return rc;
+    SoA ext = soa_of(c->ws->ext, n);
     if (n <= (size_t)c->vb_quad_max) {
       if ((rc = ensure(c, c->ws_tmp[0], 32 * n))) return rc;
       hipLaunchKernelGGL(k_fill_scalar, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, c->ws_tmp[0].p, (const uint8_t*)c->ws_tmp[1].p);
-      if ((rc = varbase_to_ext(c, n, c->ws_tmp[0].p, dp, ext, false))) return rc;
-    } else if ((rc = varbase_to_ext(c, n, c->ws_tmp[1].p, dp, ext, false, true))) return rc;
-    if ((rc = normalize_launch(c, n, ext, o.dev, 0))) return rc;
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+      if ((rc = varbase_to_ext(c, n, c->ws_tmp[0].p, din[0], ext, false))) return rc;
+    } else if ((rc = varbase_to_ext(c, n, c->ws_tmp[1].p, din[0], ext, false, true))) return rc;
+    return normalize_launch(c, n, ext, dout[0], 0);
+  });
 }
 // ---- two terms per unit: out[i] = a[i] P[i] + b[i] Q[i] in one interleaved ladder (k_varbase_mul2, jj_straus.h).  VARIABLE-TIME like the
 // _vartime entry points above (per-lane tables in memory, digit-dependent addresses).  The lane kernel serves every n (no quad form).
 // shared: `da` is ONE pair of scalars (a then b, 64 device bytes) for the whole batch, db is unused.
 static int varbase_mul2_to_ext(jj_ctx* c, size_t n, const void* da, const void* dp, const void* db, const void* dq, SoA ext, bool shared) {
-  unsigned blocks; size_t threads;
-  varbase_geometry(c, n, &blocks, &threads);
+  unsigned blocks;
   const bool w5 = c->vb_mul2_window == 5;
-  int rc = ensure(c, c->ws->tables, threads * (size_t)(w5 ? Straus<5>::LANE_WORDS : Straus<4>::LANE_WORDS) * 4); if (rc) return rc;
-  if ((rc = ensure(c, c->ws->cursor, 64))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->ws->cursor.p, 0, 8, c->stream));          // the waves' work cursor
+  int rc = ladder_workspace(c, n, w5 ? Straus<5>::LANE_WORDS : Straus<4>::LANE_WORDS, &blocks); if (rc) return rc;
   u32* tables = (u32*)c->ws->tables.p; unsigned long long* cursor = (unsigned long long*)c->ws->cursor.p;
   if (w5 && shared) hipLaunchKernelGGL((k_varbase_mul2<5, true>), dim3(blocks), dim3(256), 0, c->stream, n, da, dp, db, dq, tables, ext, cursor);
   else if (w5) hipLaunchKernelGGL((k_varbase_mul2<5, false>), dim3(blocks), dim3(256), 0, c->stream, n, da, dp, db, dq, tables, ext, cursor);
@@ -266,37 +265,9 @@ static int varbase_mul2_api(jj_ctx* c, size_t n, const void* a, const void* p, c
   if (!c) return JJ_ERR_INVALID;
   if (n && (!a || !p || !b || !q || !out)) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  if (const size_t ch = pipe_chunk_for(c, n, 18); ch && all_host({a, p, b, q, out})) {
-    const HostIn in[4] = {{a, 32}, {p, 64}, {b, 32}, {q, 64}};
-    const HostOut ho[1] = {{out, (size_t)(mode ? 32 : 64)}};
-    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
-      int rc2;
-      if ((rc2 = ensure_ext(c, cn, 3))) return rc2;
-      SoA ext = soa_of(c->ws->ext, cn);
-      if ((rc2 = varbase_mul2_to_ext(c, cn, di[0], di[1], di[2], di[3], ext, false))) return rc2;
-      if ((rc2 = pipe_to_tail(c))) return rc2;
-      return normalize_launch(c, cn, ext, dout[0], mode);
-    });
-    if (prc <= 0) return prc;      // +1: buffers could not be page-locked -> plain staging below
-  }
-  const void *da, *dp, *db, *dq; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, a, 32 * n, &da))) return rc;
-  if ((rc = stage_in(c, 1, p, 64 * n, &dp))) return rc;
-  if ((rc = stage_in(c, 2, b, 32 * n, &db))) return rc;
-  if ((rc = stage_in(c, 3, q, 64 * n, &dq))) return rc;
-  if ((rc = stage_out(c, c->out[0], out, (mode ? 32 : 64) * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    prof_mark(c, 0);
-    if ((rc = varbase_mul2_to_ext(c, n, da, dp, db, dq, ext, false))) return rc;
-    prof_mark(c, 1);
-    if ((rc = normalize_launch(c, n, ext, o.dev, mode))) return rc;
-    prof_mark(c, 2);
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_to_points(c, n, {{a, 32, 0}, {p, 64, 1}, {b, 32, 2}, {q, 64, 3}}, out, mode, 3, pipe_chunk_for(c, n, 18), 0, [&](size_t cn, const void* const* din, SoA ext) -> int {
+    return varbase_mul2_to_ext(c, cn, din[0], din[1], din[2], din[3], ext, false);
+  });
 }
 JJ_API int jj_varbase_mul2_vartime(jj_ctx* c, size_t n, const void* a32, const void* p64, const void* b32, const void* q64, void* out64) { return varbase_mul2_api(c, n, a32, p64, b32, q64, out64, 0); }
 JJ_API int jj_varbase_mul2_vartime_compressed(jj_ctx* c, size_t n, const void* a32, const void* p64, const void* b32, const void* q64, void* out32) { return varbase_mul2_api(c, n, a32, p64, b32, q64, out32, 1); }
@@ -308,47 +279,18 @@ JJ_API int jj_varbase_mul2_scalars(jj_ctx* c, size_t n, const void* ab64, const 
   if (!n) return JJ_OK;
   int rc;
   if ((rc = ensure(c, c->ws_tmp[1], 64))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->ws_tmp[1].p, ab64, 64, is_device_ptr(ab64) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-  const void* dab = c->ws_tmp[1].p;
-  if (const size_t ch = pipe_chunk_for(c, n, 18); ch && all_host({p, q, out})) {
-    const HostIn in[2] = {{p, 64}, {q, 64}};
-    const HostOut ho[1] = {{out, 64}};
-    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
-      int rc2;
-      if ((rc2 = ensure_ext(c, cn, 3))) return rc2;
-      SoA ext = soa_of(c->ws->ext, cn);
-      if ((rc2 = varbase_mul2_to_ext(c, cn, dab, di[0], nullptr, di[1], ext, true))) return rc2;
-      if ((rc2 = pipe_to_tail(c))) return rc2;
-      return normalize_launch(c, cn, ext, dout[0], 0);
-    });
-    if (prc <= 0) return prc;
-  }
-  const void *dp, *dq; OutRef o;
-  if ((rc = stage_in(c, 1, p, 64 * n, &dp))) return rc;
-  if ((rc = stage_in(c, 3, q, 64 * n, &dq))) return rc;
-  if ((rc = stage_out(c, c->out[0], out, 64 * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  prof_mark(c, 0);
-  if ((rc = varbase_mul2_to_ext(c, n, dab, dp, nullptr, dq, ext, true))) return rc;
-  prof_mark(c, 1);
-  if ((rc = normalize_launch(c, n, ext, o.dev, 0))) return rc;
-  prof_mark(c, 2);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  HIPCHK(c, hipMemcpyAsync(c->ws_tmp[1].p, ab64, 64, is_device_ptr(ab64) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));   // ahead of the pipeline's streams, which start behind c->stream
+  return run_to_points(c, n, {{p, 64, 1}, {q, 64, 3}}, out, 0, 3, pipe_chunk_for(c, n, 18), 0, [&](size_t cn, const void* const* din, SoA ext) -> int {
+    return varbase_mul2_to_ext(c, cn, c->ws_tmp[1].p, din[0], nullptr, din[1], ext, true);
+  });
 }
 JJ_API int jj_varbase_mul_exact(jj_ctx* c, size_t n, const void* scalars, const void* points, void* out160) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void *ds, *dp; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, scalars, 32 * n, &ds))) return rc;
-  if ((rc = stage_in(c, 1, points, 64 * n, &dp))) return rc;
-  if ((rc = stage_out(c, c->out[0], out160, 160 * n, &o))) return rc;
-  if (n) hipLaunchKernelGGL(k_varbase_exact, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, dp, o.dev);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{scalars, 32, 0}, {points, 64, 1}}, {{out160, 160, &c->out[0]}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    hipLaunchKernelGGL(k_varbase_exact, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], din[1], dout[0]);
+    return JJ_OK;
+  });
 }
 
 // [r]P == O for affine device points -> ok bytes (combine: 0 set, 1 and).  Default: order-8 Tate pairing
@@ -372,26 +314,36 @@ static int torsion_free_dev(jj_ctx* c, size_t n, const void* dpts, uint8_t* dok,
 static int torsion_pred(jj_ctx* c, size_t n, const void* p, uint8_t* out, bool prime_order) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void* dp; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, p, 64 * n, &dp))) return rc;
-  if ((rc = stage_out(c, c->okb, out, n, &o))) return rc;
-  if (n) {
-    if ((rc = torsion_free_dev(c, n, dp, (uint8_t*)o.dev, 0))) return rc;
+  return run_batch(c, n, {{p, 64, 0}}, {{out, 1, &c->okb}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    int rc;
+    if ((rc = torsion_free_dev(c, n, din[0], (uint8_t*)dout[0], 0))) return rc;
     if (prime_order) {   // & !is_identity  (reference src/lib.rs:717-719)
       if ((rc = ensure(c, c->ws_tmp[2], n))) return rc;
       if ((rc = ensure_ext(c, n, 3))) return rc;
-      hipLaunchKernelGGL((k_point_op<PT_IS_IDENTITY>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dp, (const void*)nullptr, soa_of(c->ws->ext, n), c->ws_tmp[2].p);
-      hipLaunchKernelGGL(k_and_bytes, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (uint8_t*)o.dev, (const uint8_t*)c->ws_tmp[2].p, 1);
+      hipLaunchKernelGGL((k_point_op<PT_IS_IDENTITY>), dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], (const void*)nullptr, soa_of(c->ws->ext, n), c->ws_tmp[2].p);
+      hipLaunchKernelGGL(k_and_bytes, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (uint8_t*)dout[0], (const uint8_t*)c->ws_tmp[2].p, 1);
     }
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+    return JJ_OK;
+  });
 }
 JJ_API int jj_is_torsion_free(jj_ctx* c, size_t n, const void* p, uint8_t* out) { return torsion_pred(c, n, p, out, false); }
 JJ_API int jj_is_prime_order(jj_ctx* c, size_t n, const void* p, uint8_t* out) { return torsion_pred(c, n, p, out, true); }
 
 // ---------------------------------------------------------------------------------------------------- fixed-base
+// the tail of every table builder: ne affine points on the host -> a device table of `bytes` bytes, entries `stride` words apart (k_affine_to_table)
+static int upload_table(jj_ctx* c, const uint8_t* aff, size_t ne, int stride, size_t bytes, u32** out_dev) {
+  u32* dev = nullptr;
+  if (hipMalloc((void**)&dev, bytes) != hipSuccess) { c->err = "hipMalloc(table) failed"; return JJ_ERR_NOMEM; }
+  const void* dpts;
+  int rc = stage_in(c, 0, aff, ne * 64, &dpts);
+  if (!rc) {
+    hipLaunchKernelGGL(k_affine_to_table, dim3(blocks_for(ne)), dim3(256), 0, c->stream, ne, dpts, dev, stride);
+    rc = finish(c, true);
+  }
+  if (rc) { (void)hipFree(dev); return rc; }
+  *out_dev = dev;
+  return JJ_OK;
+}
 // entries (i, j) = j * 2^(w i) * B for i < W, j < E (j = 0: the identity), built on the GPU in two var-base passes
 // (Q_i = 2^(w i) B, then (j+1) Q_i) so that no scalar ever reaches bit 252, which the ladder ignores.
 static int build_window_table(jj_ctx* c, const uint8_t base[64], int w, int W, u32 E, size_t extra_top_entry, u32** out_dev, size_t* out_entries) {
@@ -416,16 +368,9 @@ static int build_window_table(jj_ctx* c, const uint8_t base[64], int w, int W, u
     uint8_t sc[32] = {0}; sc[w >> 3] = (uint8_t)(1u << (w & 7));
     rc = jj_varbase_mul(c, 1, sc, &q[(size_t)(W - 1) * 64], &aff[(size_t)W * E * 64]); if (rc) return rc;
   }
-  u32* dev = nullptr;
   const int stride = extra_top_entry ? ANIELS_WORDS : GNIELS_WORDS;      // LDS-staged table: packed; gathered table: one line per entry
-  if (hipMalloc((void**)&dev, ne * (size_t)stride * 4) != hipSuccess) { c->err = "hipMalloc(table) failed"; return JJ_ERR_NOMEM; }
-  const void* dpts;
-  if ((rc = stage_in(c, 0, aff.data(), ne * 64, &dpts))) { (void)hipFree(dev); return rc; }
-  hipLaunchKernelGGL(k_affine_to_table, dim3(blocks_for(ne)), dim3(256), 0, c->stream, ne, dpts, dev, stride);
-  rc = finish(c, true);
-  if (rc) { (void)hipFree(dev); return rc; }
-  *out_dev = dev; *out_entries = ne;
-  return JJ_OK;
+  *out_entries = ne;
+  return upload_table(c, aff.data(), ne, stride, ne * (size_t)stride * 4, out_dev);
 }
 // Signed-comb table (layout of k_fixedbase_comb): 8 tables T_{j1}[idx] = 2^(4 j1) (2^224 + sum_{i<7} (2 idx_i - 1) 2^(32 i)) B of 128
 // entries, then T_0 - B and T_0 + B.  Built on the GPU through the library's own entry points: Q_i = 2^(32 i) B and
@@ -460,15 +405,7 @@ static int build_comb_table(jj_ctx* c, const uint8_t base[64], u32** out_dev) {
   for (int e = 0; e < FBC_TENT; e++) memcpy(&b64[(size_t)e * 64], base, 64);
   if ((rc = jj_point_sub(c, FBC_TENT, acc.data(), b64.data(), &all[ne * 64]))) return rc;                    // T_0 - B
   if ((rc = jj_point_add(c, FBC_TENT, acc.data(), b64.data(), &all[(ne + FBC_TENT) * 64]))) return rc;       // T_0 + B
-  u32* dev = nullptr;
-  if (hipMalloc((void**)&dev, (size_t)FBC_LDS_BYTES) != hipSuccess) { c->err = "hipMalloc(table) failed"; return JJ_ERR_NOMEM; }
-  const void* dpts;
-  if ((rc = stage_in(c, 0, all.data(), (size_t)FBC_ENTRIES * 64, &dpts))) { (void)hipFree(dev); return rc; }
-  hipLaunchKernelGGL(k_affine_to_table, dim3(blocks_for(FBC_ENTRIES)), dim3(256), 0, c->stream, (size_t)FBC_ENTRIES, dpts, dev, ANIELS_WORDS);
-  rc = finish(c, true);
-  if (rc) { (void)hipFree(dev); return rc; }
-  *out_dev = dev;
-  return JJ_OK;
+  return upload_table(c, all.data(), FBC_ENTRIES, ANIELS_WORDS, FBC_LDS_BYTES, out_dev);
 }
 JJ_API int jj_fixedbase_table_create(jj_ctx* c, const void* base64, int window_bits, jj_table** out) {
   if (!c || !out || !base64) return JJ_ERR_INVALID;
@@ -477,7 +414,7 @@ JJ_API int jj_fixedbase_table_create(jj_ctx* c, const void* base64, int window_b
   JJ_ENTER(c);
   uint8_t base[64];
   if (is_device_ptr(base64)) { HIPCHK(c, hipMemcpy(base, base64, 64, hipMemcpyDeviceToHost)); } else memcpy(base, base64, 64);
-  jj_table* t = new jj_table();
+  auto t = std::make_unique<jj_table>();
   t->window_bits = window_bits;
   t->device = c->device;
   size_t ne = 0; int rc;
@@ -493,8 +430,8 @@ JJ_API int jj_fixedbase_table_create(jj_ctx* c, const void* base64, int window_b
     for (int i = 0; i < fp.W - 1; i++) { const int bit = fp.w * i + fp.w - 1; fp.recode[bit >> 5] |= 1u << (bit & 31); }
     rc = build_window_table(c, base, fp.w, fp.W, fp.E + 1, 0, &t->dev, &ne);
   }
-  if (rc) { delete t; return rc; }
-  *out = t;
+  if (rc) return rc;
+  *out = t.release();
   return JJ_OK;
 }
 JJ_API int jj_fixedbase_table_destroy(jj_ctx* c, jj_table* t) {
@@ -502,8 +439,8 @@ JJ_API int jj_fixedbase_table_destroy(jj_ctx* c, jj_table* t) {
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  const std::unique_ptr<jj_table> owned(t);
   if (t->dev) (void)hipFree(t->dev);
-  delete t;
   return JJ_OK;
 }
 static int fixedbase_launch(jj_ctx* c, const jj_table* t, size_t n, const void* ds, SoA ext, int chain = 0) {
@@ -528,34 +465,9 @@ static int fixedbase_api(jj_ctx* c, const jj_table* t, size_t n, const void* sca
   if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
   // lanes of the table's kernel: one workgroup per CU for the LDS tables, fb_gather_blocks_per_cu blocks of 256 for the gathered ones
   const size_t fb_lanes = t->window_bits == 7 ? (size_t)c->cus * FBC_THREADS : t->window_bits == FB_W ? (size_t)c->cus * FB_THREADS : (size_t)c->cus * c->fb_gather_blocks_per_cu * 256;
-  if (const size_t ch = pipe_chunk_for(c, n, 20, fb_lanes); ch && all_host({scalars, out})) {
-    const HostIn in[1] = {{scalars, 32}};
-    const HostOut ho[1] = {{out, (size_t)(mode ? 32 : 64)}};
-    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
-      int rc2;
-      if ((rc2 = ensure_ext(c, cn, 3))) return rc2;
-      SoA ext = soa_of(c->ws->ext, cn);
-      if ((rc2 = fixedbase_launch(c, t, cn, di[0], ext))) return rc2;
-      if ((rc2 = pipe_to_tail(c))) return rc2;
-      return normalize_launch(c, cn, ext, dout[0], mode);
-    }, fb_lanes);
-    if (prc <= 0) return prc;
-  }
-  const void* ds; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, scalars, 32 * n, &ds))) return rc;
-  if ((rc = stage_out(c, c->out[0], out, (mode ? 32 : 64) * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    prof_mark(c, 0);
-    if ((rc = fixedbase_launch(c, t, n, ds, ext))) return rc;
-    prof_mark(c, 1);
-    if ((rc = normalize_launch(c, n, ext, o.dev, mode))) return rc;
-    prof_mark(c, 2);
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_to_points(c, n, {{scalars, 32, 0}}, out, mode, 3, pipe_chunk_for(c, n, 20, fb_lanes), fb_lanes, [&](size_t cn, const void* const* din, SoA ext) -> int {
+    return fixedbase_launch(c, t, cn, din[0], ext);
+  });
 }
 
 JJ_API int jj_fixedbase_mul(jj_ctx* c, const jj_table* t, size_t n, const void* scalars, void* out) { return fixedbase_api(c, t, n, scalars, out, 0); }
@@ -565,44 +477,33 @@ JJ_API int jj_fixedbase_multi_mul(jj_ctx* c, const jj_table* const* tables, int 
   for (int j = 0; j < nbases; j++) if (!tables[j]) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   for (int j = 0; j < nbases; j++) if (tables[j]->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  const void* ds; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, scalars, 32 * n * (size_t)nbases, &ds))) return rc;
-  if ((rc = stage_out(c, c->out[0], out64, 64 * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 5))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    prof_mark(c, 0);
+  return run_to_points(c, n, {{scalars, 32 * (size_t)nbases, 0}}, out64, 0, 5, 0, 0, [&](size_t n, const void* const* din, SoA ext) -> int {
     for (int j = 0; j < nbases; j++) {
       const int chain = (j > 0 ? 1 : 0) | (j + 1 < nbases ? 2 : 0);
-      if ((rc = fixedbase_launch(c, tables[j], n, (const uint8_t*)ds + (size_t)j * n * 32, ext, chain))) return rc;
+      int rc = fixedbase_launch(c, tables[j], n, (const uint8_t*)din[0] + (size_t)j * n * 32, ext, chain); if (rc) return rc;
     }
-    prof_mark(c, 1);
-    if ((rc = normalize_launch(c, n, ext, o.dev, 0))) return rc;
-    prof_mark(c, 2);
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+    return JJ_OK;
+  });
 }
 // ---- several bases, short scalars, one pass (k_pack_composite + k_fixedbase on a composite table)
 JJ_API int jj_fixedbase_composite_create(jj_ctx* c, int nbases, const void* bases64, const int* scalar_bits, jj_table** out) {
   if (!c || !out || !bases64 || !scalar_bits || nbases < 1 || nbases > FBX_MAX_BASES) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  jj_table* t = new jj_table();
+  auto t = std::make_unique<jj_table>();
   t->window_bits = FB_W;
   t->device = c->device;
   int slots = 0;
   for (int b = 0; b < nbases; b++) {
-    if (scalar_bits[b] < 1 || scalar_bits[b] > 250) { c->err = "composite table: scalar_bits must be 1..250"; delete t; return JJ_ERR_INVALID; }
+    if (scalar_bits[b] < 1 || scalar_bits[b] > 250) { c->err = "composite table: scalar_bits must be 1..250"; return JJ_ERR_INVALID; }
     t->fx.off[b] = slots; t->fx.bits[b] = scalar_bits[b];
     slots += (scalar_bits[b] + 2 + FB_W - 1) / FB_W;                 // 6 W >= bits + 2: the field's recoding never carries out of it
   }
-  if (slots > FB_NWIN) { c->err = "composite table: the bases need more than 42 six-bit windows (sum of ceil((bits + 2) / 6))"; delete t; return JJ_ERR_INVALID; }
+  if (slots > FB_NWIN) { c->err = "composite table: the bases need more than 42 six-bit windows (sum of ceil((bits + 2) / 6))"; return JJ_ERR_INVALID; }
   t->fx.nb = nbases;
   std::vector<uint8_t> bases((size_t)nbases * 64);
   if (is_device_ptr(bases64)) {
     const hipError_t e = hipMemcpy(bases.data(), bases64, bases.size(), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { c->err = std::string("hipMemcpy(bases) failed: ") + hipGetErrorString(e); delete t; return JJ_ERR_HIP; }
+    if (e != hipSuccess) { c->err = std::string("hipMemcpy(bases) failed: ") + hipGetErrorString(e); return JJ_ERR_HIP; }
   } else memcpy(bases.data(), bases64, bases.size());
   // Q_s = 64^(local window) B_b for every slot in use, then j Q_s for j = 0 .. 32; unused slots and the carry entry hold the identity
   int rc;
@@ -611,43 +512,26 @@ JJ_API int jj_fixedbase_composite_create(jj_ctx* c, int nbases, const void* base
     const int W = (b + 1 < nbases ? t->fx.off[b + 1] : slots) - t->fx.off[b];
     for (int i = 0; i < W; i++, sl++) { const int bit = FB_W * i; s1[(size_t)sl * 32 + (bit >> 3)] = (uint8_t)(1u << (bit & 7)); memcpy(&p1[(size_t)sl * 64], &bases[(size_t)b * 64], 64); }
   }
-  if ((rc = jj_varbase_mul(c, slots, s1.data(), p1.data(), q.data()))) { delete t; return rc; }
+  if ((rc = jj_varbase_mul(c, slots, s1.data(), p1.data(), q.data()))) return rc;
   const size_t ne = (size_t)slots * FB_ENT;
   std::vector<uint8_t> s2(ne * 32, 0), p2(ne * 64), aff((size_t)FB_ENTRIES * 64, 0);
   for (size_t e = 0; e < ne; e++) { s2[e * 32] = (uint8_t)(e % FB_ENT); memcpy(&p2[e * 64], &q[(e / FB_ENT) * 64], 64); }
   for (size_t e = 0; e < (size_t)FB_ENTRIES; e++) aff[e * 64 + 32] = 1;                    // affine identity (0, 1)
-  if ((rc = jj_varbase_mul(c, ne, s2.data(), p2.data(), aff.data()))) { delete t; return rc; }
+  if ((rc = jj_varbase_mul(c, ne, s2.data(), p2.data(), aff.data()))) return rc;
   for (size_t e = ne; e < (size_t)FB_ENTRIES; e++) { memset(&aff[e * 64], 0, 64); aff[e * 64 + 32] = 1; }
-  if (hipMalloc((void**)&t->dev, (size_t)FB_LDS_BYTES) != hipSuccess) { c->err = "hipMalloc(table) failed"; delete t; return JJ_ERR_NOMEM; }
-  const void* dpts;
-  if ((rc = stage_in(c, 0, aff.data(), (size_t)FB_ENTRIES * 64, &dpts))) { (void)hipFree(t->dev); delete t; return rc; }
-  hipLaunchKernelGGL(k_affine_to_table, dim3(blocks_for(FB_ENTRIES)), dim3(256), 0, c->stream, (size_t)FB_ENTRIES, dpts, t->dev, ANIELS_WORDS);
-  rc = finish(c, true);
-  if (rc) { (void)hipFree(t->dev); delete t; return rc; }
-  *out = t;
+  if ((rc = upload_table(c, aff.data(), FB_ENTRIES, ANIELS_WORDS, FB_LDS_BYTES, &t->dev))) return rc;
+  *out = t.release();
   return JJ_OK;
 }
 JJ_API int jj_fixedbase_composite_mul(jj_ctx* c, const jj_table* t, size_t n, const void* scalars, void* out64) {
   if (!c || !t || t->fx.nb < 1) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  const void* ds; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, scalars, 32 * n * (size_t)t->fx.nb, &ds))) return rc;
-  if ((rc = stage_out(c, c->out[0], out64, 64 * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  if ((rc = ensure(c, c->ws_tmp[2], 32 * std::max<size_t>(n, 1)))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    prof_mark(c, 0);
-    hipLaunchKernelGGL(k_pack_composite, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, t->fx, c->ws_tmp[2].p);
-    if ((rc = fixedbase_launch(c, t, n, c->ws_tmp[2].p, ext))) return rc;
-    prof_mark(c, 1);
-    if ((rc = normalize_launch(c, n, ext, o.dev, 0))) return rc;
-    prof_mark(c, 2);
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  int rc = ensure(c, c->ws_tmp[2], 32 * std::max<size_t>(n, 1)); if (rc) return rc;      // the packed scalars; grown ahead of the profile's first mark
+  return run_to_points(c, n, {{scalars, 32 * (size_t)t->fx.nb, 0}}, out64, 0, 3, 0, 0, [&](size_t n, const void* const* din, SoA ext) -> int {
+    hipLaunchKernelGGL(k_pack_composite, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], t->fx, c->ws_tmp[2].p);
+    return fixedbase_launch(c, t, n, c->ws_tmp[2].p, ext);
+  });
 }
 JJ_API int jj_fixedbase_mul_compressed(jj_ctx* c, const jj_table* t, size_t n, const void* scalars, void* out32) { return fixedbase_api(c, t, n, scalars, out32, 1); }
 
@@ -672,11 +556,8 @@ static int fixedvar_to_ext(jj_ctx* c, const jj_table* t, size_t n, const void* d
     if (rc) return rc;
     return fixedbase_launch(c, t, n, da, ext, /*chain=*/1);
   }
-  unsigned blocks; size_t threads;
-  varbase_geometry(c, n, &blocks, &threads);
-  int rc = ensure(c, c->ws->tables, threads * (size_t)FixedVar<VB_W>::LANE_WORDS * 4); if (rc) return rc;
-  if ((rc = ensure(c, c->ws->cursor, 64))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->ws->cursor.p, 0, 8, c->stream));          // the waves' work cursor
+  unsigned blocks;
+  int rc = ladder_workspace(c, n, FixedVar<VB_W>::LANE_WORDS, &blocks); if (rc) return rc;
   hipLaunchKernelGGL(k_varbase_fixed, dim3(blocks), dim3(256), 0, c->stream, n, da, db, dq, (const u32*)t->dev, t->fp, (u32*)c->ws->tables.p, ext, (unsigned long long*)c->ws->cursor.p);
   return JJ_OK;
 }
@@ -686,36 +567,9 @@ static int fixedvar_api(jj_ctx* c, const jj_table* t, size_t n, const void* a, c
   JJ_ENTER(c);
   if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
   if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_fixedvar_mul_vartime needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
-  if (const size_t ch = pipe_chunk_for(c, n, 18); ch && all_host({a, b, q, out})) {
-    const HostIn in[3] = {{a, 32}, {b, 32}, {q, 64}};      // the table stays resident
-    const HostOut ho[1] = {{out, (size_t)(mode ? 32 : 64)}};
-    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
-      int rc2;
-      if ((rc2 = ensure_ext(c, cn, 5))) return rc2;
-      SoA ext = soa_of(c->ws->ext, cn);
-      if ((rc2 = fixedvar_to_ext(c, t, cn, di[0], di[1], di[2], ext))) return rc2;
-      if ((rc2 = pipe_to_tail(c))) return rc2;
-      return normalize_launch(c, cn, ext, dout[0], mode);
-    });
-    if (prc <= 0) return prc;      // +1: buffers could not be page-locked -> plain staging below
-  }
-  const void *da, *db, *dq; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, a, 32 * n, &da))) return rc;
-  if ((rc = stage_in(c, 2, b, 32 * n, &db))) return rc;
-  if ((rc = stage_in(c, 3, q, 64 * n, &dq))) return rc;
-  if ((rc = stage_out(c, c->out[0], out, (mode ? 32 : 64) * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 5))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    prof_mark(c, 0);
-    if ((rc = fixedvar_to_ext(c, t, n, da, db, dq, ext))) return rc;
-    prof_mark(c, 1);
-    if ((rc = normalize_launch(c, n, ext, o.dev, mode))) return rc;
-    prof_mark(c, 2);
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_to_points(c, n, {{a, 32, 0}, {b, 32, 2}, {q, 64, 3}}, out, mode, 5, pipe_chunk_for(c, n, 18), 0, [&](size_t cn, const void* const* din, SoA ext) -> int {      // (the table stays resident)
+    return fixedvar_to_ext(c, t, cn, din[0], din[1], din[2], ext);
+  });
 }
 JJ_API int jj_fixedvar_mul_vartime(jj_ctx* c, const jj_table* t, size_t n, const void* a32, const void* b32, const void* q64, void* out64) { return fixedvar_api(c, t, n, a32, b32, q64, out64, 0); }
 JJ_API int jj_fixedvar_mul_vartime_compressed(jj_ctx* c, const jj_table* t, size_t n, const void* a32, const void* b32, const void* q64, void* out32) { return fixedvar_api(c, t, n, a32, b32, q64, out32, 1); }
@@ -766,37 +620,28 @@ JJ_API int jj_synth_bytes32(jj_ctx* c, size_t n, uint64_t seed, uint64_t first_i
 static int synth32(jj_ctx* c, size_t n, uint64_t seed, uint64_t first_index, int raw, void* out32) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  int rc; OutRef o;
-  if ((rc = stage_out(c, c->out[0], out32, 32 * n, &o))) return rc;
-  if (n) hipLaunchKernelGGL(k_synth_scalars, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)seed, (u64)first_index, raw, o.dev);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {}, {{out32, 32, &c->out[0]}}, 0, 0, [&](size_t n, const void* const*, void* const* dout, bool) -> int {
+    hipLaunchKernelGGL(k_synth_scalars, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)seed, (u64)first_index, raw, dout[0]);
+    return JJ_OK;
+  });
 }
 JJ_API int jj_random_points(jj_ctx* c, size_t n, uint64_t seed, uint64_t first_index, int subgroup, void* out64, uint32_t* attempts) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  int rc; OutRef o, ao; ao.host = false; ao.dev = nullptr;
-  if ((rc = stage_out(c, c->out[0], out64, 64 * n, &o))) return rc;
-  if (attempts && (rc = stage_out(c, c->out[1], attempts, 4 * n, &ao))) return rc;
-  if (n) hipLaunchKernelGGL(k_random_points, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)seed, (u64)first_index, subgroup ? 1 : 0, c->sqrt_tables, o.dev, (u32*)ao.dev);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  if (attempts && (rc = finish_out(c, ao, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {}, {{out64, 64, &c->out[0]}, {attempts, (size_t)(attempts ? 4 : 0), &c->out[1]}}, 0, 0, [&](size_t n, const void* const*, void* const* dout, bool) -> int {
+    hipLaunchKernelGGL(k_random_points, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)seed, (u64)first_index, subgroup ? 1 : 0, c->sqrt_tables, dout[0], (u32*)dout[1]);
+    return JJ_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------- encodings
 JJ_API int jj_compress(jj_ctx* c, size_t n, const void* points, void* out32) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void* dp; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, points, 64 * n, &dp))) return rc;
-  if ((rc = stage_out(c, c->out[0], out32, 32 * n, &o))) return rc;
-  if (n) hipLaunchKernelGGL(k_compress, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dp, o.dev);
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{points, 64, 0}}, {{out32, 32, &c->out[0]}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    hipLaunchKernelGGL(k_compress, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], dout[0]);
+    return JJ_OK;
+  });
 }
 // the decoder and the flag kernels that follow it, on device pointers (n > 0), all on c->stream
 static int decompress_dev(jj_ctx* c, size_t n, const void* di, unsigned flags, void* dout, uint8_t* dok, bool prof) {
@@ -827,38 +672,18 @@ static int decompress_dev(jj_ctx* c, size_t n, const void* di, unsigned flags, v
 JJ_API int jj_decompress(jj_ctx* c, size_t n, const void* in32, unsigned flags, void* out64, uint8_t* ok) {
   if (!c || (!ok && n)) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  if (const size_t ch = pipe_chunk_for(c, n, 21); ch && all_host({in32, out64, ok})) {
-    const HostIn in[1] = {{in32, 32}};
-    const HostOut ho[2] = {{out64, 64}, {ok, 1}};
-    const int prc = run_pipelined(c, n, ch, in, ho, [&](size_t cn, const void* const* di, void* const* dout) -> int {
-      return decompress_dev(c, cn, di[0], flags, dout[0], (uint8_t*)dout[1], false);
-    });
-    if (prc <= 0) return prc;      // +1: buffers could not be page-locked -> plain staging below
-  }
-  const void* di; int rc; OutRef o, ko;
-  if ((rc = stage_in(c, 0, in32, 32 * n, &di))) return rc;
-  if ((rc = stage_out(c, c->out[0], out64, 64 * n, &o))) return rc;
-  if ((rc = stage_out(c, c->okb, ok, n, &ko))) return rc;
-  if (n && (rc = decompress_dev(c, n, di, flags, o.dev, (uint8_t*)ko.dev, true))) return rc;
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  if ((rc = finish_out(c, ko, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{in32, 32, 0}}, {{out64, 64, &c->out[0]}, {ok, 1, &c->okb}}, pipe_chunk_for(c, n, 21), 0, [&](size_t cn, const void* const* din, void* const* dout, bool staged) -> int {
+    return decompress_dev(c, cn, din[0], flags, dout[0], (uint8_t*)dout[1], staged);
+  });
 }
 JJ_API int jj_batch_normalize(jj_ctx* c, size_t n, const void* ext160, void* out64) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  const void* de; int rc; OutRef o;
-  if ((rc = stage_in(c, 0, ext160, 160 * n, &de))) return rc;
-  if ((rc = stage_out(c, c->out[0], out64, 64 * n, &o))) return rc;
-  if ((rc = ensure_ext(c, n, 3))) return rc;
-  SoA ext = soa_of(c->ws->ext, n);
-  if (n) {
-    hipLaunchKernelGGL(k_ext160_to_soa, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, de, ext);
-    if ((rc = normalize_launch(c, n, ext, o.dev, 0))) return rc;
-  }
-  bool sync = false;
-  if ((rc = finish_out(c, o, &sync))) return rc;
-  return finish(c, sync);
+  return run_batch(c, n, {{ext160, 160, 0}}, {{out64, 64, &c->out[0]}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    int rc;
+    if ((rc = ensure_ext(c, n, 3))) return rc;
+    SoA ext = soa_of(c->ws->ext, n);
+    hipLaunchKernelGGL(k_ext160_to_soa, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], ext);
+    return normalize_launch(c, n, ext, dout[0], 0);
+  });
 }
-

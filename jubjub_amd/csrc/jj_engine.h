@@ -19,6 +19,7 @@
 #include <condition_variable>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <dlfcn.h>
 #include <unistd.h>
 
@@ -274,8 +275,11 @@ constexpr size_t BOUNCE_THRESHOLD = (size_t)1 << 20;
 constexpr size_t REGISTER_MIN_BYTES = (size_t)1 << 20;
 bool owns_its_pages(const void* p, size_t bytes);
 struct OutRef { void* user; void* dev; size_t bytes; bool host; };
-struct HostIn { const void* p; size_t elem; };
-struct HostOut { void* p; size_t elem; };
+// One per-unit array argument of a batch entry point (run_batch, jj_abi.hip): `elem` bytes per unit, 0 for an optional array that is absent.
+// A host array is staged whole in c->in[slot], or written to *buf before it is copied out; the pipeline gives every chunk its own slots.
+struct ArgIn { const void* p; size_t elem; int slot; };
+struct ArgOut { void* p; size_t elem; DevBuf* buf; };
+constexpr int ARGS_IN_MAX = 4, ARGS_OUT_MAX = 2;          // = jj_ctx::in[], the outputs of jj_decompress
 static inline SoA soa_of(DevBuf& b, size_t n) { SoA s; s.base = (u32*)b.p; s.n = n; return s; }
 static inline unsigned blocks_for(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 static const uint8_t AFFINE_IDENTITY_BYTES[64] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
@@ -291,7 +295,6 @@ int stage_out(jj_ctx* c, DevBuf& buf, void* p, size_t bytes, OutRef* o);
 int finish_out(jj_ctx* c, const OutRef& o, bool* need_sync);
 int finish(jj_ctx* c, bool need_sync);
 int pipe_prepare(jj_ctx* c, size_t in_bytes, size_t out_bytes);
-bool all_host(std::initializer_list<const void*> ptrs);
 void prefault_parallel(void* p, size_t bytes);
 size_t pipe_chunk_for(const jj_ctx* c, size_t n, int pref_log2, size_t quantum = 0);
 std::vector<size_t> pipe_chunk_bounds(size_t n, size_t CH, size_t quantum, bool ramp);
@@ -303,8 +306,8 @@ int jj_batch_init(jj_ctx* c);                          // jj_abi.hip: LDS carve-
 int msm_begin_locked(jj_ctx* c, size_t n, const void* scalars, const void* points, int part_w0, int part_stride, bool spread, jj_msm_job** out);   // jj_msm.hip
 void msm_job_put(jj_ctx* c, jj_msm_job* j);            // jj_msm.hip
 
-template <int NIN, int NOUT, class Body>
-static int run_pipelined(jj_ctx* c, size_t n, size_t CH, const HostIn (&in)[NIN], const HostOut (&out)[NOUT], Body body, size_t quantum = 0) {
+template <class Body>
+static int run_pipelined(jj_ctx* c, size_t n, size_t CH, const ArgIn* in, const int NIN, const ArgOut* out, const int NOUT, Body body, size_t quantum) {
   size_t in_stride = 0, out_stride = 0;
   for (int k = 0; k < NIN; k++) in_stride += in[k].elem;
   for (int k = 0; k < NOUT; k++) out_stride += out[k].elem;
@@ -318,8 +321,8 @@ static int run_pipelined(jj_ctx* c, size_t n, size_t CH, const HostIn (&in)[NIN]
   // Memory that is page-locked already (jj_host_alloc / hipHostMalloc, or registered by the caller -- jj_multi_* registers the whole
   // batch once before it cuts it into per-device shards, whose boundaries are not page-aligned) is copied from and to as it is.
   // Pageable arrays go through the context's staging buffers (bounce, the default) or are page-locked in place for this call.
-  bool pin_in[NIN], pin_out[NOUT], any_bounce = false;
-  void* locked[NIN + NOUT]; int nlocked = 0; bool ok = true;
+  bool pin_in[ARGS_IN_MAX], pin_out[ARGS_OUT_MAX], any_bounce = false;
+  void* locked[ARGS_IN_MAX + ARGS_OUT_MAX]; int nlocked = 0; bool ok = true;
   for (int k = 0; k < NIN; k++) pin_in[k] = is_pinned_host(in[k].p, n * in[k].elem);
   for (int k = 0; k < NOUT; k++) pin_out[k] = is_pinned_host(out[k].p, n * out[k].elem);
   if (!c->pipe_bounce) {
@@ -380,7 +383,7 @@ static int run_pipelined(jj_ctx* c, size_t n, size_t CH, const HostIn (&in)[NIN]
   for (size_t k = 0; k < nchunks; k++) {
     const int s = (int)(k & 1); const size_t lo = bounds[k], cn = bounds[k + 1] - lo;
     const int g = (int)(k % 3);
-    const void* din[NIN]; void* dout[NOUT];
+    const void* din[ARGS_IN_MAX]; void* dout[ARGS_OUT_MAX];
     size_t off = 0;
     if (k >= 2) PIPE_CHK(hipStreamWaitEvent(P.h2d, P.ev_done[s], 0));            // slot's previous kernels have consumed din[s]
     for (int j = 0; j < NIN; j++) {

@@ -321,7 +321,7 @@ class Case:
     build     n -> {input name: (rows, width) uint8}; oracle: (inputs, n) -> {output name: array | None}, None = the region must stay untouched
     options   the option sets (jj_ctx_set_option) under which the row runs
     device / host: regions that must live in device / host memory whatever the placement; host_only: runs without a GPU
-    pipelined the entry point cuts large all-host batches into chunks (run_pipelined in jj_abi.hip)
+    pipelined the entry point cuts large all-host batches into chunks (it hands run_batch in jj_abi.hip a chunk length from pipe_chunk_for)
     rc        n -> the return code the header promises; call: replaces the plain call (two-step entry points); verify: replaces the byte
               comparison of an output whose bytes are not canonical (name -> fn(got, inputs, n, lib) -> problem or None)"""
 
@@ -769,8 +769,9 @@ class Run:
     def ptr(self, name):
         return self.where[name].ptr(name)
 
-    def call(self, lib, ctx=None, env=None, n=None):
-        """the return code; n: the size handed to the entry point when it is not the size the regions were carved for"""
+    def call(self, lib, ctx=None, env=None, n=None, swap=None):
+        """the return code; n: the size handed to the entry point when it is not the size the regions were carved for; swap: {position in the
+        row's argument list: address or None} handed over in place of that pointer argument"""
         c, n = self.case, self.n if n is None else n
         if c.call is not None:
             return c.call(self, lib, ctx, env)
@@ -790,6 +791,8 @@ class Run:
                 vals.append(C.cast(self._keep, C.c_void_p))
             else:
                 vals.append(a[0](a[1](n) if callable(a[1]) else a[1]))
+        for i, address in (swap or {}).items():
+            vals[i] = C.c_void_p(address)
         types = fn.argtypes
         if types:                                   # region addresses for parameters the binding declares as typed pointers
             assert len(types) == len(vals), (c.fn, len(types), len(vals))

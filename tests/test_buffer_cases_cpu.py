@@ -59,16 +59,18 @@ def test_every_entry_point_that_writes_through_a_pointer_has_a_row():
 
 
 def pipelined_entry_points():
-    """the entry points whose body, or the shared body they forward to, calls run_pipelined (jj_abi.hip)"""
+    """the entry points whose body, or the shared body they forward to, asks pipe_chunk_for for a chunk length and hands it to the front end
+    (run_batch in jj_abi.hip, the one caller of run_pipelined)"""
     abi = open(os.path.join(BC.CSRC, "jj_abi.hip")).read()
     bodies, current = set(), None
     for line in abi.split("\n"):
         m = re.match(r"^(?:static int|JJ_API int) (\w+)\(", line)
         if m:
             current = m.group(1)
-        if "= run_pipelined(" in line:
+        if "pipe_chunk_for(" in line:
             bodies.add(current)
-    assert len(bodies) == 6 == abi.count("= run_pipelined("), bodies
+    assert len(bodies) == 6 == abi.count("pipe_chunk_for("), bodies
+    assert abi.count("run_pipelined(") == 1
     forwards = dict(re.findall(r"^JJ_API int (jj_\w+)\(.*?\) \{ return (\w+)\(", abi, flags=re.M))
     return {fn for fn in bodies if fn.startswith("jj_")} | {fn for fn, body in forwards.items() if body in bodies}
 

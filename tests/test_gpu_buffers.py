@@ -5,6 +5,7 @@ bytes, (3) leave every guard byte and every input byte as it was.  Device arenas
 ONE torch tensor.  Host arenas (pageable, one jj_host_alloc block, mixed with device memory), the chunked host pipeline, n = 0, and one positive
 control that makes a real kernel store land in a guard.  The module prints how much it checked when it finishes."""
 import os
+import re
 import sys
 
 import numpy as np
@@ -229,3 +230,55 @@ def test_positive_control_one_row_too_many(env):
     assert (guard_row("out") == written).all()
     assert run.problems(env.lib) == ["dev arena: %r" % {"kind": "guard", "region": "out", "side": "behind", "distance": 0, "count": 32}]
     STATS["calls"] += 1
+
+
+# ---- what an entry point answers to a pointer it cannot use
+def _abi_entry_points():
+    abi = open(os.path.join(BC.CSRC, "jj_abi.hip")).read()
+    return set(re.findall(r"^JJ_API int (jj_\w+)\(", abi, flags=re.M)) | set(re.findall(r"\bFIELD_(?:BIN|UN|UN_OK)\((jj_\w+),", abi))
+
+
+ABI_CASES = [c for c in GPU_CASES if c.call is None and c.fn in _abi_entry_points()]
+OPTIONAL = {("jj_random_points", "attempts")}                  # may be NULL: the one optional array of these entry points
+
+
+def refusals(case):
+    """(position, argument, kind) of every call the row is refused with: each pointer argument as NULL, and every per-unit array (the ones
+    stage_in / stage_out resolve before any launch) also as a device pointer 8 bytes past a 16-byte boundary.  A single 32- or 64-byte
+    scalar argument is copied as it is and has no alignment rule: NULL only."""
+    out = []
+    for i, a in enumerate(case.args):
+        if a == "ctx" or (isinstance(a, tuple) and a[0] in ("handle", "handles")):
+            out.append((i, a if a == "ctx" else a[0], "null"))
+        elif isinstance(a, str) and a != "n" and (case.fn, a) not in OPTIONAL:
+            out.append((i, a, "null"))
+            if case.nrows(a, 2) == 2 * case.nrows(a, 1):
+                out.append((i, a, "misaligned"))
+    return out
+
+
+@pytest.mark.parametrize("case", ABI_CASES, ids=[c.id for c in ABI_CASES])
+def test_refused_arguments(env, case):
+    """One unit on a device arena, one argument at a time made unusable (refusals): the call returns JJ_ERR_INVALID and leaves every output
+    region and every guard byte as it was, and the unmodified call that follows on the same context (checked_call) equals the oracle.
+    The expectations were recorded with the library of the commit before the entry points got their common front end, which refused every
+    one of these calls (profiles/abi_front_end_ab.txt)."""
+    assert len(ABI_CASES) >= 60 and {"jj_fq_add", "jj_decompress", "jj_point_sum", "jj_random_points", "jj_fixedvar_mul_vartime"} <= {c.fn for c in ABI_CASES}
+    options, place = case.options[0], placement(case, "dev", "dev")
+    eng = env.engine(options)
+    todo = refusals(case)
+    assert len(todo) >= 3 and todo[0] == (0, "ctx", "null")
+    for i, name, kind in todo:
+        run = Run(case, 1, place, MIXED_SKEW, env.allocs())
+        env.torch.cuda.synchronize()
+        if kind == "misaligned":
+            assert run.where[name].torch and run.ptr(name) % 16 == 0
+        rc = run.call(env.lib, env.ctx(case, eng), env, swap={i: None if kind == "null" else run.ptr(name) + 8})
+        print("refused %s %s %s: rc %d" % (case.id, name, kind, rc))
+        assert rc == BC.INVALID, (case.id, name, kind, rc)
+        assert env.lib.jj_ctx_sync(eng._ctx) == 0
+        assert all(run.where[k].untouched(k) for k, _ in case.outs), (case.id, name, kind, "an output was written")
+        assert [v for a in run.arenas.values() for v in a.violations()] == [], (case.id, name, kind)
+        STATS["calls"] += 1
+        STATS["guard_bytes"] += run.counts()[1]
+        checked_call(env, case, options, 1, place, MIXED_SKEW)
