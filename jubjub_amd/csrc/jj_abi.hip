@@ -7,8 +7,10 @@
 int jj_batch_init(jj_ctx* c) {
   // the fixed-base kernels need the full 160 KiB LDS carve-out
   const struct { const void* fn; int bytes; } lds_needs[] = {
-    {reinterpret_cast<const void*>(k_fixedbase<true>), FB_LDS_BYTES}, {reinterpret_cast<const void*>(k_fixedbase<false>), FB_LDS_BYTES},
-    {reinterpret_cast<const void*>(k_fixedbase_comb<true>), FBC_LDS_BYTES}, {reinterpret_cast<const void*>(k_fixedbase_comb<false>), FBC_LDS_BYTES},
+    {reinterpret_cast<const void*>(k_fixedbase<true>), FB_LDS_BYTES}, {reinterpret_cast<const void*>(k_fixedbase_comb<true>), FBC_LDS_BYTES},
+#ifdef JJ_EXPERIMENTS   // the gather selects of JJ_FIXEDBASE_SELECT=gather: instantiated in probe builds only (fixedbase_launch)
+    {reinterpret_cast<const void*>(k_fixedbase<false>), FB_LDS_BYTES}, {reinterpret_cast<const void*>(k_fixedbase_comb<false>), FBC_LDS_BYTES},
+#endif
     {reinterpret_cast<const void*>(k_varbase_ct3), CT3_LDS_BYTES_PER_BLOCK}};
   for (const auto& a : lds_needs)
     if (hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes) != hipSuccess) return JJ_ERR_HIP;   // the kernels could not launch later
@@ -447,15 +449,21 @@ static int fixedbase_launch(jj_ctx* c, const jj_table* t, size_t n, const void* 
   // one workgroup per CU (the table fills the LDS)
   if (t->window_bits == 7) {
     const unsigned cblocks = (unsigned)std::min((size_t)c->cus, (n + FBC_THREADS - 1) / FBC_THREADS);
-    if (c->fb_const_time) hipLaunchKernelGGL(k_fixedbase_comb<true>, dim3(cblocks), dim3(FBC_THREADS), FBC_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
-    else hipLaunchKernelGGL(k_fixedbase_comb<false>, dim3(cblocks), dim3(FBC_THREADS), FBC_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
+#ifdef JJ_EXPERIMENTS   // the per-lane gather select exists in probe builds only (JJ_FIXEDBASE_SELECT=gather); the shipped code object carries the shuffle select alone
+    if (!c->fb_const_time) hipLaunchKernelGGL(k_fixedbase_comb<false>, dim3(cblocks), dim3(FBC_THREADS), FBC_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
+    else
+#endif
+    hipLaunchKernelGGL(k_fixedbase_comb<true>, dim3(cblocks), dim3(FBC_THREADS), FBC_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
   } else if (t->window_bits != FB_W) {
     const unsigned gblocks = (unsigned)std::min((size_t)c->cus * c->fb_gather_blocks_per_cu, (n + 255) / 256);
     hipLaunchKernelGGL(k_fixedbase_gather, dim3(gblocks), dim3(256), 0, c->stream, n, ds, (const u32*)t->dev, t->fp, ext, chain);
   } else {
     const unsigned wblocks = (unsigned)std::min((size_t)c->cus, (n + FB_THREADS - 1) / FB_THREADS);
-    if (c->fb_const_time) hipLaunchKernelGGL(k_fixedbase<true>, dim3(wblocks), dim3(FB_THREADS), FB_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
-    else hipLaunchKernelGGL(k_fixedbase<false>, dim3(wblocks), dim3(FB_THREADS), FB_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
+#ifdef JJ_EXPERIMENTS
+    if (!c->fb_const_time) hipLaunchKernelGGL(k_fixedbase<false>, dim3(wblocks), dim3(FB_THREADS), FB_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
+    else
+#endif
+    hipLaunchKernelGGL(k_fixedbase<true>, dim3(wblocks), dim3(FB_THREADS), FB_LDS_BYTES, c->stream, n, ds, (const u32*)t->dev, ext, chain);
   }
   return JJ_OK;
 }

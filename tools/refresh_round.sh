@@ -65,4 +65,6 @@ timeout 400 python tests/soak_jobs.py 180 9000 > gpurun_out/${TAG}_soak_jobs.txt
 ./experiments/mad_banks/probe > gpurun_out/${TAG}_mad_banks.txt 2>&1          # multiply-add issue rate against VGPR banks, operand kinds and waves per SIMD
 ./experiments/sync_latency/probe > gpurun_out/${TAG}_sync_latency.txt 2>&1    # what the host's wait for a kernel costs: event, stream, flag in host memory
 for N in 17 18 20; do for L in 2 3 4; do for A in 2 4 6; do python bench.py --workload msm --log2n $N --msm-async $A --opt msm_lanes=$L --no-cpu-baseline --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('2^$N lanes $L async $A: %.4f ms per MSM, frac %.3f, verified %s' % (d['config']['ms_per_pass'], d['roofline']['frac'], d['verified']))"; done; done; done > gpurun_out/${TAG}_msm_lanes.txt 2>&1
+R=$(dirname */${TAG}_profile.log)                                                                                            # where this round's results are collected
+python tools/kernel_reach.py --trace $R/${TAG}_reach > $R/${TAG}_kernel_reach.log 2>&1                                          # which GPU test file launches which kernel; then, without a GPU: python tools/kernel_reach.py --ledger <that directory> -> tests/kernel_reach.json
 tail -1 gpurun_out/${TAG}_profile.log
