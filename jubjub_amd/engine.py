@@ -27,6 +27,27 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _host_bytes(x):
+    """A host argument as a contiguous uint8 array, never by a cast of its values: an array of another dtype is a TypeError (as for a torch
+    tensor), bytes-like objects are taken as they are, a sequence of integers must hold byte values."""
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint8:
+            raise TypeError("numpy arguments must be uint8, got %s" % x.dtype)
+        return np.ascontiguousarray(x)
+    if isinstance(x, memoryview) and (x.itemsize != 1 or not x.c_contiguous):
+        raise TypeError("a memoryview argument must be contiguous bytes, got format %r" % x.format)
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        return np.frombuffer(x, dtype=np.uint8)
+    a = np.asarray(x)
+    if a.size == 0:
+        return np.zeros(0, np.uint8)
+    if a.dtype.kind not in "iu":
+        raise TypeError("byte values (integers 0 ... 255) expected, got %s" % a.dtype)
+    if (a < 0).any() or (a > 255).any():
+        raise ValueError("byte values (integers 0 ... 255) expected")
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
 class _Arg:
     """Normalises one array argument to (pointer, keepalive)."""
 
@@ -45,7 +66,7 @@ class _Arg:
             self.torch = True
             self.device = x.device
         else:
-            a = np.ascontiguousarray(x, dtype=np.uint8)
+            a = _host_bytes(x)
             if width is not None and a.size % width:
                 raise ValueError("byte length %d is not a multiple of %d" % (a.size, width))
             self.n = a.size // width if width else a.size

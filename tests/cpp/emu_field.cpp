@@ -42,6 +42,25 @@ static void field_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, u
 }
 extern "C" void emu_fq_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok) { field_op<Fq>(op, a, b, out, ok); }
 extern "C" void emu_fr_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok) { field_op<Fr>(op, a, b, out, ok); }
+// Which branch of to_plain / is_zero a result takes (tests/test_field_cases_cpu.py): the class of the product mul(r, plain one) both of them form,
+// for r = add / sub / mul (op 0 / 1 / 2) of two from_words values.  0: every digit is 0; 1: the digits of -p (the only case where to_plain adds p and
+// carry_full ripples through all nine limbs down to 0); 2: anything else, r is not 0 mod p.
+template <class F, class P>
+static int plain_product_class(int op, const uint8_t* a, const uint8_t* b) {
+  u32 wa[8], wb[8];
+  ld(wa, a); ld(wb, b);
+  const Fe x = F::from_words(wa), y = F::from_words(wb);
+  const Fe r = op == 0 ? F::add(x, y) : op == 1 ? F::sub(x, y) : F::mul(x, y);
+  const Fe t = F::mul(r, F::plain_one());
+  u32 o0 = 0, o1 = 0;
+  for (int i = 0; i < NL; i++) { o0 |= t.l[i]; o1 |= t.l[i] ^ P::NEGP_DIGITS[i]; }
+  const int cls = o0 == 0 ? 0 : o1 == 0 ? 1 : 2;
+  if ((cls != 2) != F::is_zero(r)) jj_emu_overflow("is_zero disagrees with the class of its product");
+  return cls;
+}
+extern "C" int emu_plain_product_class(int fr, int op, const uint8_t* a, const uint8_t* b) {
+  return fr ? plain_product_class<Fr, FrP>(op, a, b) : plain_product_class<Fq, FqP>(op, a, b);
+}
 // from_bytes (checked) and from_bytes_wide
 extern "C" void emu_from_bytes(int fr, const uint8_t* a, uint8_t* out, uint8_t* ok) {
   u32 wa[8], wo[8]; ld(wa, a); bool k;
@@ -131,6 +150,49 @@ extern "C" int emu_normalize(const uint8_t* point, const uint8_t* scale32, uint8
   Fq::pack(w, Fq::canon_plain_product(Fq::mul(U, zp))); st(out64, w);
   Fq::pack(w, Fq::canon_plain_product(Fq::mul(V, zp))); st(out64 + 32, w);
   return (zz ? 1 : 0) | (Fq::is_zero_product(Fq::one()) ? 2 : 0) | (Fq::is_zero_product(Fq::mul(Fq::zero(), sc)) ? 0 : 4) | (Fq::is_zero(Z) != zz ? 8 : 0);
+}
+// One lane of k_normalize<CHUNK> after k_ext160_to_soa, statement for statement (the forward products, invert_divsteps, the plain-form walk back):
+// rows: chunk x 96 bytes (U, V, Z as jj_batch_normalize takes them), out: chunk x 64 bytes, adds[2 j], adds[2 j + 1]: how many times
+// canon_plain_product added q to row j's u and v (0, 1 or 2)
+static int canon_adds(const Fe& a) {
+  Fe w = a; int count = 0;
+  for (int rep = 0; rep < 2; rep++) {
+    const u32 negm = (u32)((i32)w.l[NL - 1] >> 31);
+    count += (int)(negm & 1u);
+    Fe s; for (int i = 0; i < NL; i++) s.l[i] = w.l[i] + (FqP::P[i] & negm);
+    w = Fq::carry_full(s);
+  }
+  // this loop is a copy of canon_plain_product's with a counter: it must end where the library's function ends, limb for limb
+  const Fe lib = Fq::canon_plain_product(a);
+  for (int i = 0; i < NL; i++) if (w.l[i] != lib.l[i]) { jj_emu_overflow("canon_adds is no longer canon_plain_product"); break; }
+  return count;
+}
+extern "C" void emu_normalize_lane(int chunk, const uint8_t* rows, uint8_t* out, int* adds) {
+  Fe U[64], V[64], Z[64], scratch[64];
+  if (chunk > 64) { jj_emu_overflow("emu_normalize_lane: chunk"); return; }
+  for (int j = 0; j < chunk; j++) {
+    u32 w[8];
+    ld(w, rows + 96 * j); U[j] = Fq::from_words(w);
+    ld(w, rows + 96 * j + 32); V[j] = Fq::from_words(w);
+    ld(w, rows + 96 * j + 64); Z[j] = Fq::from_words(w);
+  }
+  Fe acc = Fq::one();
+  for (int j = 0; j < chunk; j++) {
+    scratch[j] = acc;
+    const u32 zz = Fq::is_zero_product(Z[j]) ? ~0u : 0u;
+    acc = Fq::select(Fq::mul(acc, Z[j]), acc, zz);
+  }
+  Fe inv = Fq::mul(Fq::invert_divsteps(acc), Fq::plain_one());
+  for (int j = chunk - 1; j >= 0; j--) {
+    const u32 zz = Fq::is_zero_product(Z[j]) ? ~0u : 0u;
+    const Fe zp = Fq::select(Fq::mul(inv, scratch[j]), Fq::zero(), zz);
+    inv = Fq::select(Fq::mul(inv, Z[j]), inv, zz);
+    const Fe pu = Fq::mul(U[j], zp), pv = Fq::mul(V[j], zp);
+    adds[2 * j] = canon_adds(pu); adds[2 * j + 1] = canon_adds(pv);
+    u32 w[8];
+    Fq::pack(w, Fq::canon_plain_product(pu)); st(out + 64 * j, w);
+    Fq::pack(w, Fq::canon_plain_product(pv)); st(out + 64 * j + 32, w);
+  }
 }
 extern "C" int emu_predicates(const uint8_t* point) {
   const Affine a = load_affine(point);

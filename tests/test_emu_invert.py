@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import jubjub_ref as J
+from field_cases import inversion_values
 from tests.util import arr32, to_int
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,10 +60,10 @@ def _check(emu, field, ops, a, b, values):
 @pytest.mark.parametrize("field", ["Fq", "Fr"])
 def test_edge_values(emu, field):
     p = FIELDS[field][1]
-    xs = [0, 1, p - 1, 2, p - 2, p - 1]
-    for k in range(255):
-        xs += [1 << k, (1 << k) - 1]
-    xs += [p, p + 1, (1 << 256) - 1]                      # from_words reduces any 256-bit integer
+    X = list(inversion_values(field.lower()))              # the list the device inverts too (tests/test_gpu_field_matrix.py)
+    assert {1, 2, 3, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2} <= set(X)
+    assert all(1 << k in X and (k < 3 or (1 << k) - 1 in X) for k in range(255))   # as integers, not reduced: 2^252 ... 2^254 exceed Fr's modulus
+    xs = [0] + X + [p, p + 1, (1 << 256) - 1]              # zero, and from_words reduces any 256-bit integer
     zeros = np.zeros((len(xs), 32), np.uint8)
     _check(emu, field, np.zeros(len(xs), np.uint8), arr32(xs), zeros, xs)
 
