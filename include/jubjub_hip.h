@@ -495,6 +495,32 @@ int jj_msm_allgather(jj_ctx*, size_t n, const void* scalars32, const void* point
  * may be finished in any order, each exactly once; at most 2^24 terms per rank and job; device input arrays stay valid until the
  * job is finished. */
 int jj_msm_allgather_begin(jj_ctx*, size_t n, const void* scalars32, const void* points64, int partition, jj_msm_job** job);
+/* Batch verification of n Schnorr / RedJubjub-style signatures (R_i, s_i) under keys A_i and challenges c_i, as ONE MSM job:
+ *   out64 = to_affine([8] * (sum_i [z_i] R_i + sum_i [z_i c_i mod r] A_i - [sum_i z_i s_i mod r] B))     written by jj_msm_finish(job, out64)
+ *   base64   the affine base point B: any on-curve point, also one with a cofactor component (the library knows no particular generator)
+ *   r32 a32  n compressed encodings each: the signature's R and the verification key A
+ *   s32      n response scalars (canonical: s_i >= r is malformed)
+ *   c32      n challenges as raw 32-byte integers, reduced mod r here (the caller hashes; the library knows no hash)
+ *   z16      n x 16 bytes of the caller's randomness, one 128-bit weight per signature (the library has no RNG; use non-zero weights)
+ *   flags    0 or JJ_DECOMPRESS_ZIP216 (the decoder's rule for R and A)
+ * Reducing the scalars mod r is exact because the cofactor is cleared at the end: [8][x]P = [x mod r][8]P for every P on the curve.
+ * The verdict is the point:
+ *   (0, 1)    every signature satisfies the COFACTORED check [8]([s]B - R - [c]A) = O (a torsion component of R, A or B is accepted, as
+ *             by a per-signature cofactored verifier); with random z a batch holding a failing signature gives this with chance <= 2^-128;
+ *   (0, -1)   malformed input: an encoding that does not decode under `flags`, or some s_i >= r.  [8] of anything lies in the prime-order
+ *             subgroup, so the order-2 point cannot be a sum: the sentinel is unambiguous.  A failed decode contributes the identity;
+ *   other     at least one signature fails: bisect, or check one by one with jj_fixedvar_mul_vartime_compressed.
+ * VARIABLE-TIME: everything here is public.  Device work: the decoder over r32 and a32 into a workspace the job owns, one kernel that
+ * writes the 2n scalars and a partial of sum z_i s_i per workgroup (k_sig_terms), one workgroup that closes the sum and writes the term of B
+ * and the malformed flag (k_sig_close), then the 2n + 1 terms as a job of jj_msm_begin: context lock, lanes, stream rules and lifetime are
+ * jj_msm_begin's; several jobs may be in flight and be finished in any order; the job owns its workspace until it is finished (96 bytes per
+ * term; it stays with the pooled job afterwards).  Pointers may be host or device, mixed freely (device pointers 16-byte aligned; host
+ * arrays are staged before the call returns).  n = 0 gives a job whose finish writes the identity (the arrays may then be NULL).
+ * JJ_ERR_INVALID before any device work, *job = NULL: a NULL context, job or base64, a NULL array with n > 0, flags other than 0 or
+ * JJ_DECOMPRESS_ZIP216, 2n + 1 > 2^24.  No synchronous twin, no per-signature ok array.
+ * Measured on an MI355X (profiles/sig_batch_ab.txt, device-resident valid batches, signatures/s, median of five alternating rounds): 2^20 signatures 140.8 M/s with one job (7.45 ms) and 178.3 M/s with four in flight, against 26.7 M/s for the same check composed from jj_decompress x 2, jj_fr_mul, a host-side sum and jj_msm (5.3x / 6.7x) and 55.7 M/s for the per-signature route jj_decompress x 2 + jj_point_neg + jj_fixedvar_mul_vartime_compressed, table 13 (2.5x / 3.2x); 2^16: 23.9 M/s (one job) and 45.1 M/s (four) against 23.9 composed and 27.1 per signature -- one job alone is 12 % BEHIND the per-signature route there, the two decodes of 2^14 lanes each are its serial chain; 2^10: 1.68 / 2.12 M/s against 1.13 and 0.95.  Both routes decode 2n points: the decoder, not the MSM, is the larger part of this call. */
+int jj_sigbatch_begin(jj_ctx*, const void* base64, size_t n, const void* r32, const void* a32, const void* s32, const void* c32, const void* z16,
+                      unsigned flags, jj_msm_job** job);
 
 /* ---- encodings ----------------------------------------------------------------------------------------- */
 #define JJ_DECOMPRESS_ZIP216          1u  /* reject the two non-canonical encodings (src/lib.rs:469-471, 522-531) */

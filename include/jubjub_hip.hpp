@@ -22,6 +22,7 @@
 // Results cross the boundary as the crate's own public encodings, so they can be fed straight back into the Rust
 // types with Fq::from_bytes / AffinePoint::from_raw_unchecked.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -380,6 +381,13 @@ class MsmJob {
     if (p_.size() != s_.size()) throw Error(JJ_ERR_INVALID, "length mismatch");
     c.check(jj_msm_allgather_begin(c.raw(), p_.size(), s_.data(), p_.data(), how.by_windows ? 1 : 0, &job_));
   }
+  // the batch check of n Schnorr signatures as one MSM job (jj_sigbatch_begin; sigbatch_begin below): host arrays, staged at begin
+  MsmJob(const Context& c, const Bytes64& base, const std::vector<Bytes32>& R, const std::vector<Bytes32>& A, const std::vector<Bytes32>& s,
+         const std::vector<Bytes32>& ch, const std::vector<std::array<uint8_t, 16>>& z, bool zip216) : c_(&c) {
+    const size_t n = R.size();
+    if (A.size() != n || s.size() != n || ch.size() != n || z.size() != n) throw Error(JJ_ERR_INVALID, "length mismatch");
+    c.check(jj_sigbatch_begin(c.raw(), base.data(), n, R.data(), A.data(), s.data(), ch.data(), z.data(), zip216 ? JJ_DECOMPRESS_ZIP216 : 0u, &job_));
+  }
   MsmJob(const MsmJob&) = delete;
   MsmJob& operator=(const MsmJob&) = delete;
   ~MsmJob() { if (job_) { Bytes64 sink; (void)jj_msm_finish(job_, sink.data()); } }
@@ -398,6 +406,25 @@ class MsmJob {
   std::vector<Bytes64> p_;
   jj_msm_job* job_ = nullptr;
 };
+// Batch verification of Schnorr signatures (jj_sigbatch_begin): R, A compressed, s canonical responses, ch raw challenges (reduced mod r),
+// z the caller's 128-bit random weights.  The job's finish() is [8] (sum [z_i] R_i + sum [z_i c_i] A_i - [sum z_i s_i] B).
+enum class SigVerdict { Ok, Reject, Malformed };      // (0, 1) | any other point | (0, -1)
+using Bytes16 = std::array<uint8_t, 16>;
+inline std::unique_ptr<MsmJob> sigbatch_begin(const Context& c, const Bytes64& base, const std::vector<Bytes32>& R, const std::vector<Bytes32>& A,
+                                              const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z, bool zip216 = false) {
+  return std::unique_ptr<MsmJob>(new MsmJob(c, base, R, A, s, ch, z, zip216));
+}
+inline SigVerdict sigbatch_verdict(const Bytes64& out) {
+  static const Bytes32 minus_one = {{0x00, 0x00, 0x00, 0x00, 0xff, 0xff, 0xff, 0xff, 0xfe, 0x5b, 0xfe, 0xff, 0x02, 0xa4, 0xbd, 0x53, 0x05, 0xd8, 0xa1, 0x09, 0x08, 0xd8, 0x39, 0x33,
+                                     0x48, 0x7d, 0x9d, 0x29, 0x53, 0xa7, 0xed, 0x73}};      // q - 1
+  for (int i = 0; i < 32; i++) if (out[i]) return SigVerdict::Reject;
+  if (out[32] == 1 && std::all_of(out.begin() + 33, out.end(), [](uint8_t b) { return b == 0; })) return SigVerdict::Ok;
+  return std::equal(minus_one.begin(), minus_one.end(), out.begin() + 32) ? SigVerdict::Malformed : SigVerdict::Reject;
+}
+inline SigVerdict sigbatch_verify(const Context& c, const Bytes64& base, const std::vector<Bytes32>& R, const std::vector<Bytes32>& A,
+                                  const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z, bool zip216 = false) {
+  return sigbatch_verdict(sigbatch_begin(c, base, R, A, s, ch, z, zip216)->finish());
+}
 // MSM cut into parts (jj_msm_partial / jj_msm_combine): part g of G by windows (every part sees all terms) or all windows of a slice
 // of the terms; the records are combined in one host tail
 using MsmRecord = std::array<uint8_t, JJ_MSM_PARTIAL_BYTES>;

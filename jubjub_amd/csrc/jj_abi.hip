@@ -652,7 +652,7 @@ JJ_API int jj_compress(jj_ctx* c, size_t n, const void* points, void* out32) {
   });
 }
 // the decoder and the flag kernels that follow it, on device pointers (n > 0), all on c->stream
-static int decompress_dev(jj_ctx* c, size_t n, const void* di, unsigned flags, void* dout, uint8_t* dok, bool prof) {
+int decompress_dev(jj_ctx* c, size_t n, const void* di, unsigned flags, void* dout, uint8_t* dok, bool prof) {
   int rc;
   if ((rc = ensure(c, c->ws->scratch, (size_t)NL * 4 * n))) return rc;
   SoA scratch = soa_of(c->ws->scratch, n);

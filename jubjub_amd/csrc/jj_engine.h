@@ -129,7 +129,11 @@ struct jj_msm_job {
   void* gdev = nullptr; size_t gdev_cap = 0;
   int gathered = 0;             // records the all_gather delivers (0: a local job)
   bool folded = false;          // the fold kernel was queued: host holds the ONE folded record, or a zero header if the layouts differ
+  // a job of jj_sigbatch_begin: gdev holds the 2n + 1 prepared terms; the finish clears the cofactor (three doublings) and reads the malformed
+  // flag k_sig_close left in the last MSM_JOB_TAIL_BYTES of `host`
+  bool sig = false;
 };
+constexpr size_t MSM_JOB_TAIL_BYTES = 64;      // page-locked bytes behind a job's records
 
 struct jj_ctx {
   std::recursive_mutex mu;       // every entry point locks its context: calls from several host threads are serialised
@@ -302,6 +306,7 @@ size_t msm_host_pass_terms(size_t n, int pass_log2, bool split);
 int pipe_to_tail(jj_ctx* c);
 int stage_ensure(jj_ctx* c, size_t in_bytes, size_t out_bytes);
 int stage_in_drain(jj_ctx* c, size_t seq);
+int decompress_dev(jj_ctx* c, size_t n, const void* di, unsigned flags, void* dout, uint8_t* dok, bool prof);   // jj_abi.hip: the decoder on device pointers, on c->stream
 int jj_batch_init(jj_ctx* c);                          // jj_abi.hip: LDS carve-outs of the fixed-base kernels, square-root tables (called by jj_ctx_create)
 int msm_begin_locked(jj_ctx* c, size_t n, const void* scalars, const void* points, int part_w0, int part_stride, bool spread, jj_msm_job** out);   // jj_msm.hip
 void msm_job_put(jj_ctx* c, jj_msm_job* j);            // jj_msm.hip

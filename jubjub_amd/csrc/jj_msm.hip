@@ -1,6 +1,7 @@
 // libjubjub_hip.so: multi-scalar multiplication (kernels: jj_msm_kernels.h; host tail: jj_host_tail.h).
 #define JJ_KERNELS_MSM
 #include "jj_engine.h"
+#include "jj_sig_kernels.h"
 
 // MSM on the device up to the record of partial window sums (jj_msm_kernels.h); everything here is launches only (the
 // workspaces are grown first), so a pass can be queued behind another one without any host synchronisation in between.
@@ -283,14 +284,14 @@ static int msm_job_get(jj_ctx* c, size_t nrec, jj_msm_job** out) {
     j->c = c;
     if (hipEventCreateWithFlags(&j->ev, hipEventDisableTiming) != hipSuccess) { delete j; c->err = "hipEventCreate failed"; return JJ_ERR_HIP; }
   }
-  const size_t want = std::max<size_t>(nrec, 1) * jjhost::REC_MAX_BYTES;
+  const size_t want = std::max<size_t>(nrec, 1) * jjhost::REC_MAX_BYTES + MSM_JOB_TAIL_BYTES;
   if (j->cap < want) {
     if (j->host) (void)hipHostFree(j->host);
     j->host = nullptr; j->cap = 0;
     if (hipHostMalloc((void**)&j->host, want, hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); if (j->gdev) (void)hipFree(j->gdev); (void)hipEventDestroy(j->ev); delete j; c->err = "hipHostMalloc failed"; return JJ_ERR_NOMEM; }
     j->cap = want;
   }
-  j->nrec = 0; j->gathered = 0; j->folded = false;
+  j->nrec = 0; j->gathered = 0; j->folded = false; j->sig = false;
   for (size_t r = 0; r < std::max<size_t>(nrec, 1); r++) memset(j->host + r * jjhost::REC_MAX_BYTES, 0, jjhost::REC_HDR_BYTES);   // a stale header of a pooled buffer must never validate
   *out = j;
   return JJ_OK;
@@ -366,6 +367,68 @@ JJ_API int jj_msm_begin(jj_ctx* c, size_t n, const void* scalars, const void* po
   JJ_ENTER(c);
   return msm_begin_locked(c, n, scalars, points, 0, 1, true, job);
 }
+// ---- batch Schnorr verification as one MSM job (kernels: jj_sig_kernels.h).  The 2n + 1 terms are prepared on the context's stream in a
+// workspace the JOB owns (gdev: points | scalars | ok bytes | partials | B | staged host inputs), then msm_begin_locked queues the sum on a lane
+// like any device-pointer job; jj_msm_finish clears the cofactor and turns k_sig_close's flag into the (0, -1) sentinel.
+static size_t sig_up(size_t x) { return (x + 255) & ~(size_t)255; }
+JJ_API int jj_sigbatch_begin(jj_ctx* c, const void* base64, size_t n, const void* r32, const void* a32, const void* s32, const void* c32, const void* z16, unsigned flags, jj_msm_job** job) {
+  if (job) *job = nullptr;
+  if (!c || !job || !base64 || (flags & ~(unsigned)JJ_DECOMPRESS_ZIP216)) return JJ_ERR_INVALID;
+  if (n && (!r32 || !a32 || !s32 || !c32 || !z16)) return JJ_ERR_INVALID;
+  if (n > (((size_t)1 << 24) - 1) / 2) return JJ_ERR_INVALID;                    // 2n + 1 terms: one pass of the MSM
+  JJ_ENTER(c);
+  if (n == 0) return msm_begin_locked(c, 0, nullptr, nullptr, 0, 1, true, job);   // the empty sum: [8] O = O
+  const size_t T = 2 * n + 1;
+  const u32 nblk = blocks_for(n, SIG_THREADS);
+  const struct { const void* p; size_t elem; } arr[5] = {{r32, 32}, {a32, 32}, {s32, 32}, {c32, 32}, {z16, 16}};
+  bool dev[5];
+  for (int k = 0; k < 5; k++) {
+    dev[k] = is_device_ptr(arr[k].p);
+    if (dev[k] && ((uintptr_t)arr[k].p & 15u)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += sig_up(bytes); return o; };
+  const size_t o_pts = take(T * 64), o_scal = take(T * 32), o_ok = take(2 * n), o_part = take((size_t)nblk * SIG_PART_WORDS * 4), o_base = take(64);
+  size_t o_in[5];
+  for (int k = 0; k < 5; k++) o_in[k] = dev[k] ? 0 : take(n * arr[k].elem);
+  // The job: taken from the pool, given its workspace, and put back, so that msm_begin_locked (which takes the pool's last job) hands out this
+  // one: its page-locked buffer and its workspace are known before the kernels that write to them are queued.
+  const size_t PASS = msm_host_pass_terms(T, c->msm_pass_log2, false);
+  jj_msm_job* j0 = nullptr;
+  int rc = msm_job_get(c, (T + PASS - 1) / PASS, &j0); if (rc) return rc;
+  if (j0->gdev_cap < off) {
+    if (j0->gdev) (void)hipFree(j0->gdev);
+    j0->gdev = nullptr; j0->gdev_cap = 0;
+    if (hipMalloc(&j0->gdev, off) != hipSuccess) { (void)hipGetLastError(); msm_job_put(c, j0); c->err = "hipMalloc failed"; return JJ_ERR_NOMEM; }
+    j0->gdev_cap = off;
+  }
+  uint8_t* g = (uint8_t*)j0->gdev;
+  uint8_t* const host0 = j0->host;
+  u32* flag = (u32*)(j0->host + j0->cap - MSM_JOB_TAIL_BYTES);
+  *flag = 2u;                                                                     // neither verdict: k_sig_close has not run
+  msm_job_put(c, j0);
+  if (c->job_pool.empty() || c->job_pool.back() != j0) { c->err = "jj_sigbatch_begin: the job pool is full"; return JJ_ERR_HIP; }   // (the pool held fewer than 8 jobs: one was just taken)
+  auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };   // kernels may still be writing into the pooled job's buffers
+  const void* in[5];
+  for (int k = 0; k < 5; k++) {
+    const size_t bytes = n * arr[k].elem;
+    if (dev[k]) { in[k] = arr[k].p; continue; }
+    if (bytes >= BOUNCE_THRESHOLD && !is_pinned_host(arr[k].p, bytes)) { if ((rc = host_to_dev_bounced(c, g + o_in[k], arr[k].p, bytes))) return fail(rc); }
+    else if (hipMemcpyAsync(g + o_in[k], arr[k].p, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_begin: staging copy failed"; return fail(JJ_ERR_HIP); }
+    in[k] = g + o_in[k];
+  }
+  if (hipMemcpyAsync(g + o_base, base64, 64, is_device_ptr(base64) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_begin: staging copy failed"; return fail(JJ_ERR_HIP); }
+  if ((rc = decompress_dev(c, n, in[0], flags, g + o_pts, g + o_ok, false))) return fail(rc);
+  if ((rc = decompress_dev(c, n, in[1], flags, g + o_pts + 64 * n, g + o_ok + n, false))) return fail(rc);
+  hipLaunchKernelGGL(k_sig_terms, dim3(nblk), dim3(SIG_THREADS), 0, c->stream, n, in[2], in[3], in[4], (const uint8_t*)(g + o_ok), (void*)(g + o_pts), (void*)(g + o_scal), (u32*)(g + o_part));
+  hipLaunchKernelGGL(k_sig_close, dim3(1), dim3(SIG_CLOSE_THREADS), 0, c->stream, n, nblk, (const u32*)(g + o_part), (const u32*)(g + o_base), (void*)(g + o_pts), (void*)(g + o_scal), flag);
+  jj_msm_job* j = nullptr;
+  if ((rc = msm_begin_locked(c, T, g + o_scal, g + o_pts, 0, 1, true, &j))) return fail(rc);
+  if (j != j0 || j->host != host0) { (void)hipEventSynchronize(j->ev); (void)hipStreamSynchronize(c->stream); msm_job_put(c, j); c->err = "jj_sigbatch_begin: the job changed hands"; return JJ_ERR_HIP; }
+  j->sig = true;
+  *job = j;
+  return JJ_OK;
+}
 // waits for the job's records, host tail, result to out64 (host pointer: written before the call returns; device pointer: a
 // 64-byte copy queued on the context's stream).  The job is released in every case.
 JJ_API int jj_msm_finish(jj_msm_job* j, void* out64) {
@@ -388,17 +451,31 @@ JJ_API int jj_msm_finish(jj_msm_job* j, void* out64) {
       j->nrec = (size_t)j->gathered;
     }
   }
-  const bool ok = e == hipSuccess && jjhost::combine_records(j->host, j->nrec, jjhost::REC_MAX_BYTES, &total);
+  bool ok = e == hipSuccess && jjhost::combine_records(j->host, j->nrec, jjhost::REC_MAX_BYTES, &total);
+  // a job of jj_sigbatch_begin: [8] of the sum, or the order-2 point (0, -1) when k_sig_close flagged a malformed unit
+  bool malformed = false;
+  if (ok && j->sig) {
+    uint32_t flag; memcpy(&flag, j->host + j->cap - MSM_JOB_TAIL_BYTES, 4);
+    if (flag > 1u) ok = false;                                       // never written
+    malformed = flag == 1u;
+    for (int k = 0; k < 3; k++) total = jjhost::point_dbl(total);
+  }
+  auto write64 = [&](uint8_t* dst) {
+    if (!malformed) { jjhost::to_affine64(dst, total); return; }
+    memset(dst, 0, 32);
+    uint64_t v[4] = {jjhost::QL[0] - 1, jjhost::QL[1], jjhost::QL[2], jjhost::QL[3]};
+    memcpy(dst + 32, v, 32);
+  };
   JJ_ENTER(c);
   int rc = JJ_OK;
   if (e != hipSuccess) { c->err = std::string("hipEventSynchronize failed: ") + hipGetErrorString(e); rc = JJ_ERR_HIP; }
   else if (!ok) { c->err = "MSM record is damaged (bad header)"; rc = JJ_ERR_HIP; }
   else if (is_device_ptr(out64)) {
-    jjhost::to_affine64(c->host_out[c->host_out_next], total);
+    write64(c->host_out[c->host_out_next]);
     e = hipMemcpyAsync(out64, c->host_out[c->host_out_next], 64, hipMemcpyHostToDevice, c->stream);
     c->host_out_next = (c->host_out_next + 1) % 8;
     if (e != hipSuccess) { c->err = std::string("hipMemcpyAsync failed: ") + hipGetErrorString(e); rc = JJ_ERR_HIP; }
-  } else jjhost::to_affine64((uint8_t*)out64, total);
+  } else write64((uint8_t*)out64);
   msm_job_put(c, j);
   return rc;
 }

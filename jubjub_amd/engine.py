@@ -122,6 +122,41 @@ def _msm_ragged_shapes(scalars, points, offsets):
     return o.size - 1, ss[0]
 
 
+def _sigbatch_z(n):
+    """n x 16 bytes from the operating system's generator (secrets), every z_i non-zero"""
+    import secrets
+
+    z = np.frombuffer(secrets.token_bytes(16 * n), dtype=np.uint8).reshape(n, 16).copy()
+    for i in np.nonzero(~z.any(axis=1))[0]:
+        while not z[i].any():
+            z[i] = np.frombuffer(secrets.token_bytes(16), dtype=np.uint8)
+    return z
+
+
+def _sigbatch_args(base, R, A, s, c, z):
+    """jj_sigbatch_begin's arguments, checked before any C call: base 64 bytes; R, A, s, c of shape (n, 32); z of shape (n, 16) or None.
+    -> (n, [_Arg of base, R, A, s, c, z])"""
+    shapes = [tuple(x.shape) if hasattr(x, "shape") else None for x in (base, R, A, s, c)]
+    if shapes[0] not in ((64,), (1, 64)):
+        raise ValueError("base: one affine point of shape (64,) expected, got %r" % (shapes[0],))
+    if shapes[1] is None or len(shapes[1]) != 2 or shapes[1][1] != 32:
+        raise ValueError("R: shape (n, 32) expected, got %r" % (shapes[1],))
+    n = shapes[1][0]
+    for name, sh in zip(("A", "s", "c"), shapes[2:]):
+        if sh != (n, 32):
+            raise ValueError("%s: shape (%d, 32) expected, got %r" % (name, n, sh))
+    if 2 * n + 1 > 1 << 24:
+        raise ValueError("at most %d signatures per job (2n + 1 terms of one MSM pass), got %d" % (((1 << 24) - 1) // 2, n))
+    if z is None:
+        z = _sigbatch_z(n)
+    elif not hasattr(z, "shape") or tuple(z.shape) != (n, 16):
+        raise ValueError("z: shape (%d, 16) expected, got %r" % (n, tuple(z.shape) if hasattr(z, "shape") else None))
+    return n, [_Arg(x, w) for x, w in zip((base, R, A, s, c, z), (64, 32, 32, 32, 32, 16))]
+
+
+SIGBATCH_IDENTITY = bytes(32) + bytes([1]) + bytes(31)
+SIGBATCH_MALFORMED = bytes(32) + (0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001 - 1).to_bytes(32, "little")
+
 _MSM_BASIS_MODES = {"auto": 0, "points": 1, "windows": 2, 0: 0, 1: 1, 2: 2}
 
 
@@ -686,6 +721,23 @@ class Engine:
         h = C.c_void_p()
         self._check(self._lib.jj_msm_begin(self._ctx, C.c_size_t(a.n), a.ptr, p.ptr, C.byref(h)))
         return MsmJob(h, (a.keep, p.keep))
+
+    def sigbatch_begin(self, base, R, A, s, c, z=None, zip216=False):
+        """Queues the batch check of n Schnorr signatures as ONE MSM job (jj_sigbatch_begin): R, A compressed points (n, 32), s responses and
+        c challenges (n, 32; c is reduced mod r), base the affine point B (64,), z the (n, 16) random weights -- drawn from `secrets`, every
+        z_i non-zero, when None.  numpy arrays or torch CUDA tensors, mixed freely.  msm_finish(job) returns
+        [8] (sum [z_i] R_i + sum [z_i c_i] A_i - [sum z_i s_i] B): (0, 1) when every signature passes the cofactored check, (0, -1) for
+        malformed input, any other point when a signature fails.  VARIABLE-TIME; everything here is public."""
+        n, args = _sigbatch_args(base, R, A, s, c, z)
+        self._bind_stream(args)
+        h = C.c_void_p()
+        self._check(self._lib.jj_sigbatch_begin(self._ctx, args[0].ptr, C.c_size_t(n), *[a.ptr for a in args[1:]], C.c_uint(FLAG_ZIP216 if zip216 else 0), C.byref(h)))
+        return MsmJob(h, tuple(a.keep for a in args))
+
+    def sigbatch_verify(self, base, R, A, s, c, z=None, zip216=False):
+        """sigbatch_begin + msm_finish -> "ok" | "reject" | "malformed" """
+        out = self.msm_finish(self.sigbatch_begin(base, R, A, s, c, z, zip216)).tobytes()
+        return "ok" if out == SIGBATCH_IDENTITY else "malformed" if out == SIGBATCH_MALFORMED else "reject"
 
     def msm_finish(self, job):
         """-> the 64-byte affine sum as a numpy array (host memory)."""

@@ -199,6 +199,18 @@ impl Gpu {
         assert_eq!(unsafe { jj_msm_begin(self.0, scalars.len(), s.as_ptr() as _, p.as_ptr() as _, &mut job) }, 0);
         MsmJob { job, _keep: (s, p) }                       // host arrays are staged at begin; kept alive until finish anyway
     }
+    /// Batch verification of `n` Schnorr signatures as one MSM job (`jj_sigbatch_begin`): `r`, `a` compressed points, `s` responses,
+    /// `c` raw challenges (reduced mod r by the library), `z` the caller's 128-bit random weights.  `msm_finish` returns
+    /// `[8] (sum [z_i] R_i + sum [z_i c_i] A_i - [sum z_i s_i] B)`: the identity when every signature passes the cofactored check, `(0, -1)`
+    /// for malformed input, any other point when one fails.  Variable-time; everything is public.
+    pub fn sigbatch_begin(&self, base: &AffinePoint, r: &[[u8; 32]], a: &[[u8; 32]], s: &[Fr], c: &[[u8; 32]], z: &[[u8; 16]], zip216: bool) -> MsmJob {
+        let n = r.len();
+        assert!(a.len() == n && s.len() == n && c.len() == n && z.len() == n);
+        let (b, ss) = (put_points(std::slice::from_ref(base)), put_scalars(s));
+        let mut job: *mut JjMsmJob = std::ptr::null_mut();
+        assert_eq!(unsafe { jj_sigbatch_begin(self.0, b.as_ptr() as _, n, r.as_ptr() as _, a.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, z.as_ptr() as _, if zip216 { 1 } else { 0 }, &mut job) }, 0);
+        MsmJob { job, _keep: (b, ss) }                      // host arrays are staged at begin
+    }
     pub fn msm_finish(&self, j: MsmJob) -> AffinePoint {
         let mut out = [0u8; 64];
         assert_eq!(unsafe { jj_msm_finish(j.job, out.as_mut_ptr() as _) }, 0);
