@@ -521,6 +521,33 @@ int jj_msm_allgather_begin(jj_ctx*, size_t n, const void* scalars32, const void*
  * Measured on an MI355X (profiles/sig_batch_ab.txt, device-resident valid batches, signatures/s, median of five alternating rounds): 2^20 signatures 140.8 M/s with one job (7.45 ms) and 178.3 M/s with four in flight, against 26.7 M/s for the same check composed from jj_decompress x 2, jj_fr_mul, a host-side sum and jj_msm (5.3x / 6.7x) and 55.7 M/s for the per-signature route jj_decompress x 2 + jj_point_neg + jj_fixedvar_mul_vartime_compressed, table 13 (2.5x / 3.2x); 2^16: 23.9 M/s (one job) and 45.1 M/s (four) against 23.9 composed and 27.1 per signature -- one job alone is 12 % BEHIND the per-signature route there, the two decodes of 2^14 lanes each are its serial chain; 2^10: 1.68 / 2.12 M/s against 1.13 and 0.95.  Both routes decode 2n points: the decoder, not the MSM, is the larger part of this call. */
 int jj_sigbatch_begin(jj_ctx*, const void* base64, size_t n, const void* r32, const void* a32, const void* s32, const void* c32, const void* z16,
                       unsigned flags, jj_msm_job** job);
+/* The same batch check for signatures GROUPED BY KEY, with the terms of equal keys folded into one: n + K + 1 terms and n + K decodes for n
+ * signatures under K keys (a validator set, a few signers of many messages), against 2n + 1 and 2n of jj_sigbatch_begin:
+ *   out64 = to_affine([8] * (sum_i [z_i] R_i + sum_k [sum_{i in group k} z_i c_i mod r] A_k - [sum_i z_i s_i mod r] B))     written by jj_msm_finish(job, out64)
+ *   a32      K compressed verification keys
+ *   offsets  K + 1 values in HOST memory, CSR as in jj_msm_ragged: offsets[0] = 0, non-decreasing, n = offsets[K]; signatures
+ *            offsets[k] .. offsets[k+1] are checked under key k.  Read before the call returns.
+ *   r32 s32 c32 (n x 32), z16 (n x 16), base64, flags: as in jj_sigbatch_begin, in the grouped order.
+ * The verdict is the point, as there: (0, 1) accept, (0, -1) malformed, any other point a failing signature.  For every input in which each
+ * listed key has at least one signature, out64 equals BYTE FOR BYTE what jj_sigbatch_begin writes for the expanded arrays (a32[k] repeated over
+ * its group) with the same z16: the two sums differ only by multiples of [r]A_k (the folded scalar is reduced mod r once, not once per
+ * signature), and the three doublings of the finish clear those: [8][r]P = O for every P on the curve.
+ *   Empty group: a key with no signatures contributes [0]A_k.  Undecodable key: EVERY key given is decoded, and one that does not decode under
+ *   `flags` makes the batch malformed even if its group is empty.  Duplicate key: the same encoding listed twice is two groups, no special path.
+ *   n = 0 (offsets[K] = 0, any K): a job whose finish writes the identity; the arrays are not read (no key is decoded) and may be NULL.
+ * JJ_ERR_INVALID before any device work, *job = NULL: a NULL context, job or base64; NULL offsets with K > 0; a NULL array with n > 0;
+ * offsets[0] != 0 or a decreasing pair; offsets in device memory; flags other than 0 or JJ_DECOMPRESS_ZIP216; n + K + 1 > 2^24.
+ * Pointers may be host or device, mixed freely (offsets host only; device pointers 16-byte aligned, "device pointers must be 16-byte aligned"
+ * otherwise).  VARIABLE-TIME: everything here is public.  Device work: r32 and a32 copied into one region of the job's workspace and ONE
+ * decoder launch over the n + K encodings; k_sig_keyed_terms (jj_sig_keyed_kernels.h), one signature per lane, writes the n scalars z_i and adds
+ * z_i c_i over the lanes of its wave that share a key; k_sig_keyed_close, one key per lane and a whole wave for a key whose group spans
+ * several waves, writes the K folded scalars; k_sig_close writes the term of B and the malformed flag; then the n + K + 1 terms as a job of
+ * jj_msm_begin.  Context lock, lanes, stream rules, job pool, workspace ownership and lifetime are jj_sigbatch_begin's (96 bytes per term
+ * and 64 more per signature -- head slot and encoding copy -- in the job's workspace); several jobs may be in flight and be finished in any order.  No synchronous twin, no per-signature
+ * ok array.
+ * Measured on an MI355X (profiles/sig_keyed_ab.txt, against jj_sigbatch_begin on the expanded arrays, device-resident valid batches in equal groups, signatures/s, median of five alternating rounds, every ratio outside the rounds' spread): 2^20 signatures, K = 8 / 256 / n/4: 176.6 / 180.7 / 174.9 M/s with one job against 145.6-146.9 (1.21x / 1.23x / 1.19x) and 293.7 / 301.8 / 285.9 M/s with four in flight against 181.0-183.5 (1.62x / 1.65x / 1.58x); 2^16: 1.25-1.33x (one job) and 1.31-1.37x (four); 2^10: 1.41-1.54x and 1.57-1.77x.  K = n at 2^20 is BEHIND: 130.7 against 146.8 M/s with one job (12 % slower), 177.1 against 183.5 with four (3.5 % slower) -- the same decodes and terms plus a copy and one more kernel; the routes cross near K = 0.67 n (interpolated).  One job gains 19 %, not half, at K = 256: the decoder launch over n + K encodings measured ~3.1 ms where one over n takes 2.03 (unexplained). */
+int jj_sigbatch_keyed_begin(jj_ctx*, const void* base64, size_t K, const void* a32, const uint64_t* offsets, const void* r32, const void* s32, const void* c32, const void* z16,
+                            unsigned flags, jj_msm_job** job);
 
 /* ---- encodings ----------------------------------------------------------------------------------------- */
 #define JJ_DECOMPRESS_ZIP216          1u  /* reject the two non-canonical encodings (src/lib.rs:469-471, 522-531) */

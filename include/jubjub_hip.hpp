@@ -388,6 +388,13 @@ class MsmJob {
     if (A.size() != n || s.size() != n || ch.size() != n || z.size() != n) throw Error(JJ_ERR_INVALID, "length mismatch");
     c.check(jj_sigbatch_begin(c.raw(), base.data(), n, R.data(), A.data(), s.data(), ch.data(), z.data(), zip216 ? JJ_DECOMPRESS_ZIP216 : 0u, &job_));
   }
+  // the same check for signatures grouped by key (jj_sigbatch_keyed_begin; sigbatch_keyed_begin below): offsets.size() == keys.size() + 1
+  MsmJob(const Context& c, const Bytes64& base, const std::vector<Bytes32>& keys, const std::vector<uint64_t>& offsets, const std::vector<Bytes32>& R,
+         const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<std::array<uint8_t, 16>>& z, bool zip216) : c_(&c) {
+    const size_t n = R.size();
+    if (offsets.size() != keys.size() + 1 || offsets.back() != n || s.size() != n || ch.size() != n || z.size() != n) throw Error(JJ_ERR_INVALID, "length mismatch");
+    c.check(jj_sigbatch_keyed_begin(c.raw(), base.data(), keys.size(), keys.data(), offsets.data(), R.data(), s.data(), ch.data(), z.data(), zip216 ? JJ_DECOMPRESS_ZIP216 : 0u, &job_));
+  }
   MsmJob(const MsmJob&) = delete;
   MsmJob& operator=(const MsmJob&) = delete;
   ~MsmJob() { if (job_) { Bytes64 sink; (void)jj_msm_finish(job_, sink.data()); } }
@@ -414,6 +421,13 @@ inline std::unique_ptr<MsmJob> sigbatch_begin(const Context& c, const Bytes64& b
                                               const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z, bool zip216 = false) {
   return std::unique_ptr<MsmJob>(new MsmJob(c, base, R, A, s, ch, z, zip216));
 }
+// The same for signatures grouped by key (jj_sigbatch_keyed_begin): signatures offsets[k] .. offsets[k+1] are checked under keys[k]; n + K + 1
+// terms.  The same 64 bytes as sigbatch_begin on the expanded arrays whenever every key has a signature.
+inline std::unique_ptr<MsmJob> sigbatch_keyed_begin(const Context& c, const Bytes64& base, const std::vector<Bytes32>& keys, const std::vector<uint64_t>& offsets,
+                                                    const std::vector<Bytes32>& R, const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z,
+                                                    bool zip216 = false) {
+  return std::unique_ptr<MsmJob>(new MsmJob(c, base, keys, offsets, R, s, ch, z, zip216));
+}
 inline SigVerdict sigbatch_verdict(const Bytes64& out) {
   static const Bytes32 minus_one = {{0x00, 0x00, 0x00, 0x00, 0xff, 0xff, 0xff, 0xff, 0xfe, 0x5b, 0xfe, 0xff, 0x02, 0xa4, 0xbd, 0x53, 0x05, 0xd8, 0xa1, 0x09, 0x08, 0xd8, 0x39, 0x33,
                                      0x48, 0x7d, 0x9d, 0x29, 0x53, 0xa7, 0xed, 0x73}};      // q - 1
@@ -424,6 +438,11 @@ inline SigVerdict sigbatch_verdict(const Bytes64& out) {
 inline SigVerdict sigbatch_verify(const Context& c, const Bytes64& base, const std::vector<Bytes32>& R, const std::vector<Bytes32>& A,
                                   const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z, bool zip216 = false) {
   return sigbatch_verdict(sigbatch_begin(c, base, R, A, s, ch, z, zip216)->finish());
+}
+inline SigVerdict sigbatch_keyed_verify(const Context& c, const Bytes64& base, const std::vector<Bytes32>& keys, const std::vector<uint64_t>& offsets,
+                                        const std::vector<Bytes32>& R, const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z,
+                                        bool zip216 = false) {
+  return sigbatch_verdict(sigbatch_keyed_begin(c, base, keys, offsets, R, s, ch, z, zip216)->finish());
 }
 // MSM cut into parts (jj_msm_partial / jj_msm_combine): part g of G by windows (every part sees all terms) or all windows of a slice
 // of the terms; the records are combined in one host tail

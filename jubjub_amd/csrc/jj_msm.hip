@@ -2,6 +2,7 @@
 #define JJ_KERNELS_MSM
 #include "jj_engine.h"
 #include "jj_sig_kernels.h"
+#include "jj_sig_keyed_kernels.h"
 
 // MSM on the device up to the record of partial window sums (jj_msm_kernels.h); everything here is launches only (the
 // workspaces are grown first), so a pass can be queued behind another one without any host synchronisation in between.
@@ -425,6 +426,90 @@ JJ_API int jj_sigbatch_begin(jj_ctx* c, const void* base64, size_t n, const void
   jj_msm_job* j = nullptr;
   if ((rc = msm_begin_locked(c, T, g + o_scal, g + o_pts, 0, 1, true, &j))) return fail(rc);
   if (j != j0 || j->host != host0) { (void)hipEventSynchronize(j->ev); (void)hipStreamSynchronize(c->stream); msm_job_put(c, j); c->err = "jj_sigbatch_begin: the job changed hands"; return JJ_ERR_HIP; }
+  j->sig = true;
+  *job = j;
+  return JJ_OK;
+}
+// ---- the same check for signatures grouped by key (kernels: jj_sig_keyed_kernels.h): n + K + 1 terms, n + K decodes in ONE decoder launch over
+// r32 | a32 copied into one region of the job's workspace (gdev: points | scalars | ok bytes | partials | B | run heads | encodings | offsets |
+// staged host inputs).  k_sig_close is launched with n = 0 on pointers moved to term n + K: it adds the partials of both kernels before it.
+// The offsets of a call, checked without a context or a device: CSR, offsets[0] = 0, non-decreasing, n + K + 1 terms in one pass of the MSM.
+static bool sig_keyed_offsets_ok(size_t K, const uint64_t* off, size_t* n) {
+  const uint64_t MAXT = (uint64_t)1 << 24;
+  *n = 0;
+  if (K >= MAXT) return false;
+  if (!off) return K == 0;
+  if (off[0] != 0) return false;
+  for (size_t k = 0; k < K; k++) if (off[k + 1] < off[k]) return false;
+  if (off[K] > MAXT - 1 - K) return false;
+  *n = (size_t)off[K];
+  return true;
+}
+JJ_API int jj_sigbatch_keyed_begin(jj_ctx* c, const void* base64, size_t K, const void* a32, const uint64_t* offsets, const void* r32, const void* s32, const void* c32, const void* z16,
+                                   unsigned flags, jj_msm_job** job) {
+  if (job) *job = nullptr;
+  if (!c || !job || !base64 || (flags & ~(unsigned)JJ_DECOMPRESS_ZIP216)) return JJ_ERR_INVALID;
+  size_t n = 0;
+  if (K >= ((size_t)1 << 24) || (K && !offsets) || (offsets && is_device_ptr(offsets)) || !sig_keyed_offsets_ok(K, offsets, &n)) return JJ_ERR_INVALID;
+  if (n && (!a32 || !r32 || !s32 || !c32 || !z16)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (n == 0) return msm_begin_locked(c, 0, nullptr, nullptr, 0, 1, true, job);   // the empty sum: [8] O = O
+  const size_t T = n + K + 1;
+  const u32 nblk = blocks_for(n, SIG_THREADS), kblk = blocks_for(K, SIG_THREADS);
+  const struct { const void* p; size_t rows, elem; } arr[5] = {{r32, n, 32}, {a32, K, 32}, {s32, n, 32}, {c32, n, 32}, {z16, n, 16}};
+  bool dev[5];
+  for (int k = 0; k < 5; k++) {
+    dev[k] = is_device_ptr(arr[k].p);
+    if (dev[k] && ((uintptr_t)arr[k].p & 15u)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += sig_up(bytes); return o; };
+  const size_t o_pts = take(T * 64), o_scal = take(T * 32), o_ok = take(n + K), o_part = take((size_t)(nblk + kblk) * SIG_PART_WORDS * 4), o_base = take(64);
+  const size_t o_heads = take(n * 32), o_enc = take((n + K) * 32), o_offs = take((K + 1) * 8);
+  size_t o_in[5] = {o_enc, o_enc + 32 * n, 0, 0, 0};                               // R and A always land in the decoder's one input region
+  for (int k = 2; k < 5; k++) o_in[k] = dev[k] ? 0 : take(n * arr[k].elem);
+  // the job: taken, given its workspace and put back, as in jj_sigbatch_begin
+  const size_t PASS = msm_host_pass_terms(T, c->msm_pass_log2, false);
+  jj_msm_job* j0 = nullptr;
+  int rc = msm_job_get(c, (T + PASS - 1) / PASS, &j0); if (rc) return rc;
+  if (j0->gdev_cap < off) {
+    if (j0->gdev) (void)hipFree(j0->gdev);
+    j0->gdev = nullptr; j0->gdev_cap = 0;
+    if (hipMalloc(&j0->gdev, off) != hipSuccess) { (void)hipGetLastError(); msm_job_put(c, j0); c->err = "hipMalloc failed"; return JJ_ERR_NOMEM; }
+    j0->gdev_cap = off;
+  }
+  uint8_t* g = (uint8_t*)j0->gdev;
+  uint8_t* const host0 = j0->host;
+  u32* flag = (u32*)(j0->host + j0->cap - MSM_JOB_TAIL_BYTES);
+  *flag = 2u;                                                                     // neither verdict: k_sig_close has not run
+  msm_job_put(c, j0);
+  if (c->job_pool.empty() || c->job_pool.back() != j0) { c->err = "jj_sigbatch_keyed_begin: the job pool is full"; return JJ_ERR_HIP; }
+  auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };   // kernels may still be writing into the pooled job's buffers
+  auto to_dev = [&](void* dst, const void* src, size_t bytes, bool src_dev) -> int {
+    if (!bytes) return JJ_OK;
+    if (!src_dev && bytes >= BOUNCE_THRESHOLD && !is_pinned_host(src, bytes)) return host_to_dev_bounced(c, dst, src, bytes);
+    if (hipMemcpyAsync(dst, src, bytes, src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_keyed_begin: staging copy failed"; return JJ_ERR_HIP; }
+    return JJ_OK;
+  };
+  const void* in[5];
+  for (int k = 0; k < 5; k++) {
+    if (k >= 2 && dev[k]) { in[k] = arr[k].p; continue; }
+    if ((rc = to_dev(g + o_in[k], arr[k].p, arr[k].rows * arr[k].elem, dev[k]))) return fail(rc);
+    in[k] = g + o_in[k];
+  }
+  if ((rc = to_dev(g + o_offs, offsets, (K + 1) * 8, false)) || (rc = to_dev(g + o_base, base64, 64, is_device_ptr(base64)))) return fail(rc);
+  if ((rc = decompress_dev(c, n + K, g + o_enc, flags, g + o_pts, g + o_ok, false))) return fail(rc);
+  const unsigned long long* doffs = (const unsigned long long*)(g + o_offs);
+  u32* part = (u32*)(g + o_part);
+  hipLaunchKernelGGL(k_sig_keyed_terms, dim3(nblk), dim3(SIG_THREADS), 0, c->stream, n, (u32)K, doffs, in[2], in[3], in[4], (const uint8_t*)(g + o_ok), (void*)(g + o_pts), (void*)(g + o_scal),
+                     (void*)(g + o_heads), part);
+  hipLaunchKernelGGL(k_sig_keyed_close, dim3(kblk), dim3(SIG_THREADS), 0, c->stream, n, (u32)K, doffs, (const uint8_t*)(g + o_ok), (const void*)(g + o_heads), (void*)(g + o_pts), (void*)(g + o_scal),
+                     part + (size_t)nblk * SIG_PART_WORDS);
+  hipLaunchKernelGGL(k_sig_close, dim3(1), dim3(SIG_CLOSE_THREADS), 0, c->stream, (size_t)0, nblk + kblk, (const u32*)part, (const u32*)(g + o_base), (void*)(g + o_pts + (n + K) * 64),
+                     (void*)(g + o_scal + (n + K) * 32), flag);
+  jj_msm_job* j = nullptr;
+  if ((rc = msm_begin_locked(c, T, g + o_scal, g + o_pts, 0, 1, true, &j))) return fail(rc);
+  if (j != j0 || j->host != host0) { (void)hipEventSynchronize(j->ev); (void)hipStreamSynchronize(c->stream); msm_job_put(c, j); c->err = "jj_sigbatch_keyed_begin: the job changed hands"; return JJ_ERR_HIP; }
   j->sig = true;
   *job = j;
   return JJ_OK;

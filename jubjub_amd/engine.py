@@ -154,6 +154,51 @@ def _sigbatch_args(base, R, A, s, c, z):
     return n, [_Arg(x, w) for x, w in zip((base, R, A, s, c, z), (64, 32, 32, 32, 32, 16))]
 
 
+def _sigbatch_keyed_args(base, keys, offsets, R, s, c, z):
+    """jj_sigbatch_keyed_begin's arguments, checked before any C call: base 64 bytes; keys (K, 32); offsets K + 1 integers (CSR, offsets[-1] = n);
+    R, s, c of shape (n, 32); z of shape (n, 16) or None.  -> (K, n, offsets as a host uint64 array, [_Arg of base, keys, R, s, c, z])"""
+    shapes = [tuple(x.shape) if hasattr(x, "shape") else None for x in (base, keys, R, s, c)]
+    if shapes[0] not in ((64,), (1, 64)):
+        raise ValueError("base: one affine point of shape (64,) expected, got %r" % (shapes[0],))
+    if shapes[1] is None or len(shapes[1]) != 2 or shapes[1][1] != 32:
+        raise ValueError("keys: shape (K, 32) expected, got %r" % (shapes[1],))
+    K = shapes[1][0]
+    o = _ragged_offsets(offsets)
+    if o.size != K + 1:
+        raise ValueError("offsets: %d values expected for %d keys, got %d" % (K + 1, K, o.size))
+    n = int(o[-1])
+    for name, sh in zip(("R", "s", "c"), shapes[2:]):
+        if sh != (n, 32):
+            raise ValueError("%s: shape (%d, 32) expected (offsets[-1] signatures), got %r" % (name, n, sh))
+    if n + K + 1 > 1 << 24:
+        raise ValueError("at most 2^24 terms per job (n + K + 1 of one MSM pass), got %d" % (n + K + 1))
+    if z is None:
+        z = _sigbatch_z(n)
+    elif not hasattr(z, "shape") or tuple(z.shape) != (n, 16):
+        raise ValueError("z: shape (%d, 16) expected, got %r" % (n, tuple(z.shape) if hasattr(z, "shape") else None))
+    return K, n, o, [_Arg(x, w) for x, w in zip((base, keys, R, s, c, z), (64, 32, 32, 32, 32, 16))]
+
+
+def _group_by_key(A):
+    """Per-signature keys (n, 32) (numpy, or a torch tensor, which is copied to the host) -> (keys, offsets, order) for sigbatch_keyed_begin:
+    keys (K, 32) the distinct encodings in lexicographic order of their bytes, offsets (K + 1,) uint64, order (n,) a STABLE permutation
+    (signatures of one key keep their order): the caller passes R[order], s[order], c[order], z[order].  Pure numpy."""
+    if _is_torch(A):
+        A = A.cpu().numpy()
+    A = np.ascontiguousarray(A, dtype=np.uint8)
+    if A.ndim != 2 or A.shape[1] != 32:
+        raise ValueError("A: shape (n, 32) expected, got %r" % (A.shape,))
+    n = A.shape[0]
+    if n == 0:
+        return np.zeros((0, 32), np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.int64)
+    rows = A.view(np.dtype((np.void, 32))).reshape(n)
+    order = np.argsort(rows, kind="stable")
+    srt = A[order]
+    first = np.concatenate([[True], (srt[1:] != srt[:-1]).any(axis=1)])
+    starts = np.nonzero(first)[0]
+    return srt[starts], np.concatenate([starts, [n]]).astype(np.uint64), order.astype(np.int64)
+
+
 SIGBATCH_IDENTITY = bytes(32) + bytes([1]) + bytes(31)
 SIGBATCH_MALFORMED = bytes(32) + (0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001 - 1).to_bytes(32, "little")
 
@@ -739,6 +784,24 @@ class Engine:
         out = self.msm_finish(self.sigbatch_begin(base, R, A, s, c, z, zip216)).tobytes()
         return "ok" if out == SIGBATCH_IDENTITY else "malformed" if out == SIGBATCH_MALFORMED else "reject"
 
+    def sigbatch_keyed_begin(self, base, keys, offsets, R, s, c, z=None, zip216=False):
+        """sigbatch_begin for signatures grouped by key (jj_sigbatch_keyed_begin): keys (K, 32) compressed verification keys, offsets K + 1
+        integers (CSR, host): signatures offsets[k] .. offsets[k+1] of R, s, c, z are checked under keys[k].  The terms of equal keys are folded:
+        n + K + 1 MSM terms and n + K decodes.  msm_finish(job) returns the same 64 bytes as sigbatch_begin on the expanded arrays whenever every
+        key has a signature; a key with none contributes nothing, but must decode.  group_by_key builds keys, offsets and the order from
+        per-signature keys.  VARIABLE-TIME; everything here is public."""
+        K, n, o, args = _sigbatch_keyed_args(base, keys, offsets, R, s, c, z)
+        self._bind_stream(args)
+        h = C.c_void_p()
+        self._check(self._lib.jj_sigbatch_keyed_begin(self._ctx, args[0].ptr, C.c_size_t(K), args[1].ptr, o.ctypes.data, *[a.ptr for a in args[2:]],
+                                                      C.c_uint(FLAG_ZIP216 if zip216 else 0), C.byref(h)))
+        return MsmJob(h, tuple(a.keep for a in args))
+
+    def sigbatch_keyed_verify(self, base, keys, offsets, R, s, c, z=None, zip216=False):
+        """sigbatch_keyed_begin + msm_finish -> "ok" | "reject" | "malformed" """
+        out = self.msm_finish(self.sigbatch_keyed_begin(base, keys, offsets, R, s, c, z, zip216)).tobytes()
+        return "ok" if out == SIGBATCH_IDENTITY else "malformed" if out == SIGBATCH_MALFORMED else "reject"
+
     def msm_finish(self, job):
         """-> the 64-byte affine sum as a numpy array (host memory)."""
         if job._h is None:
@@ -876,6 +939,7 @@ def _locked(fn):
 for _name, _fn in list(vars(Engine).items()):
     if callable(_fn) and not _name.startswith("__"):
         setattr(Engine, _name, _locked(_fn))
+Engine.group_by_key = staticmethod(_group_by_key)      # no context, no lock: Engine.group_by_key(A) or eng.group_by_key(A)
 
 
 class MultiEngine:

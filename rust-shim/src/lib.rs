@@ -211,6 +211,18 @@ impl Gpu {
         assert_eq!(unsafe { jj_sigbatch_begin(self.0, b.as_ptr() as _, n, r.as_ptr() as _, a.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, z.as_ptr() as _, if zip216 { 1 } else { 0 }, &mut job) }, 0);
         MsmJob { job, _keep: (b, ss) }                      // host arrays are staged at begin
     }
+    /// The same check for signatures grouped by key (`jj_sigbatch_keyed_begin`): `keys` the `K` compressed verification keys, `offsets` the
+    /// `K + 1` CSR offsets (`offsets[0] = 0`, non-decreasing, `offsets[K] = n`); signatures `offsets[k] .. offsets[k+1]` of `r`, `s`, `c`, `z` are
+    /// checked under `keys[k]`.  The terms of equal keys are folded: `n + K + 1` MSM terms and `n + K` decodes.  `msm_finish` returns the same
+    /// point as `sigbatch_begin` on the expanded arrays whenever every key has a signature.  Variable-time; everything is public.
+    pub fn sigbatch_keyed_begin(&self, base: &AffinePoint, keys: &[[u8; 32]], offsets: &[u64], r: &[[u8; 32]], s: &[Fr], c: &[[u8; 32]], z: &[[u8; 16]], zip216: bool) -> MsmJob {
+        let n = r.len();
+        assert!(offsets.len() == keys.len() + 1 && offsets[keys.len()] as usize == n && s.len() == n && c.len() == n && z.len() == n);
+        let (b, ss) = (put_points(std::slice::from_ref(base)), put_scalars(s));
+        let mut job: *mut JjMsmJob = std::ptr::null_mut();
+        assert_eq!(unsafe { jj_sigbatch_keyed_begin(self.0, b.as_ptr() as _, keys.len(), keys.as_ptr() as _, offsets.as_ptr(), r.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, z.as_ptr() as _, if zip216 { 1 } else { 0 }, &mut job) }, 0);
+        MsmJob { job, _keep: (b, ss) }                      // host arrays and the offsets are staged at begin
+    }
     pub fn msm_finish(&self, j: MsmJob) -> AffinePoint {
         let mut out = [0u8; 64];
         assert_eq!(unsafe { jj_msm_finish(j.job, out.as_mut_ptr() as _) }, 0);

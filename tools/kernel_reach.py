@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """
-The kernel reach ledger: which GPU test file launches which kernel of the library (tests/kernel_reach_ledger.json).
-tests/kernel_reach.json is the first ledger, of the commit that introduced the contract; it is kept as it was and no longer read.
+The kernel reach ledger: which GPU test file launches which kernel of the library (profiles/kernel_reach_ledger.json).
+The ledger is a record of a trace and lives beside the other records under profiles/, where a change that adds a kernel can write it again.
+tests/kernel_reach.json and tests/kernel_reach_ledger.json are the ledgers of earlier commits; they are kept as they were and no longer read.
 
   python tools/kernel_reach.py --trace DIR [--files test_gpu_a.py,test_gpu_b.py]     on the GPU box
       For every tests/test_gpu_*.py except test_gpu_dist.py (it only spawns bench.py ranks): one untraced pytest process, timed, then
@@ -12,7 +13,7 @@ tests/kernel_reach.json is the first ledger, of the commit that introduced the c
       faults, aborts or runs into its limit and starts nothing more on the GPU after it; a file whose tests fail is recorded as failed.
   python tools/kernel_reach.py --ledger DIR                                          no GPU (compiles the library's assembly, ~2 minutes)
       Matches the traced names of namespace jj against the .amdhsa_kernel symbols of tools/gfx_asm.assembly() -- both brought to one form
-      with one demangler (llvm-cxxfilt of the ROCm toolchain, c++filt where that is not installed), `.kd` stripped -- and writes tests/kernel_reach_ledger.json.  A traced jj kernel that no compiled
+      with one demangler (llvm-cxxfilt of the ROCm toolchain, c++filt where that is not installed), `.kd` stripped -- and writes profiles/kernel_reach_ledger.json.  A traced jj kernel that no compiled
       kernel matches is an error.
   python tools/kernel_reach.py DIR                                                   both in turn
   python tools/kernel_reach.py --check                                               no GPU: the committed ledger as a table
@@ -30,7 +31,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LEDGER = os.path.join(ROOT, "tests", "kernel_reach_ledger.json")
+LEDGER = os.path.join(ROOT, "profiles", "kernel_reach_ledger.json")
 CXXFILT = ("/opt/rocm/llvm/bin/llvm-cxxfilt", "llvm-cxxfilt", "c++filt")     # the first one installed; both sides of the match go through the same one
 SKIP = {"test_gpu_dist.py"}
 STOP = {124: "time limit", 137: "time limit (killed)", 134: "abort", 139: "segmentation fault", -6: "abort", -11: "segmentation fault", -9: "killed"}
