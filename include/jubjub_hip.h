@@ -548,6 +548,35 @@ int jj_sigbatch_begin(jj_ctx*, const void* base64, size_t n, const void* r32, co
  * Measured on an MI355X (profiles/sig_keyed_ab.txt, against jj_sigbatch_begin on the expanded arrays, device-resident valid batches in equal groups, signatures/s, median of five alternating rounds, every ratio outside the rounds' spread): 2^20 signatures, K = 8 / 256 / n/4: 176.6 / 180.7 / 174.9 M/s with one job against 145.6-146.9 (1.21x / 1.23x / 1.19x) and 293.7 / 301.8 / 285.9 M/s with four in flight against 181.0-183.5 (1.62x / 1.65x / 1.58x); 2^16: 1.25-1.33x (one job) and 1.31-1.37x (four); 2^10: 1.41-1.54x and 1.57-1.77x.  K = n at 2^20 is BEHIND: 130.7 against 146.8 M/s with one job (12 % slower), 177.1 against 183.5 with four (3.5 % slower) -- the same decodes and terms plus a copy and one more kernel; the routes cross near K = 0.67 n (interpolated).  One job gains 19 %, not half, at K = 256: the decoder launch over n + K encodings measured ~3.1 ms where one over n takes 2.03 (unexplained). */
 int jj_sigbatch_keyed_begin(jj_ctx*, const void* base64, size_t K, const void* a32, const uint64_t* offsets, const void* r32, const void* s32, const void* c32, const void* z16,
                             unsigned flags, jj_msm_job** job);
+/* S batch checks over consecutive runs of ONE signature array, one verdict point per run, in one call: what a verifier needs to find the failing
+ * signatures of a batch (bisection, Engine.sigbatch_locate) and to give many small batches a verdict each (the signatures of each transaction of
+ * a block, of each peer's message).  Synchronous in the sense of jj_msm_ragged.
+ *   offsets  S + 1 values in HOST memory, CSR as in jj_msm_ragged: offsets[0] = 0, non-decreasing, n = offsets[S]; segment g holds signatures
+ *            offsets[g] .. offsets[g+1].  Read before the call returns.
+ *   r32 a32 s32 c32 (n x 32), z16 (n x 16), base64, flags (0 or JJ_DECOMPRESS_ZIP216): as in jj_sigbatch_begin.
+ *   out64    S x 64 bytes, host or device.
+ * out64[g] equals BYTE FOR BYTE what jj_sigbatch_begin + jj_msm_finish write for the arrays of segment g alone with the same z16 rows: (0, 1)
+ * accept, and also an empty segment; (0, -1) when a unit of that segment does not decode or has s >= r; otherwise the point
+ * [8](sum z R + sum [z c mod r] A - [sum z s mod r] B) of that segment.  A malformed unit spoils its own segment only.  S = 0 succeeds and
+ * touches nothing; n = 0 with S > 0 writes S identities and reads no array (they may be NULL).
+ * Use non-zero weights.  A segment of ONE signature with a non-zero weight is an EXACT cofactored check of that signature, not a probabilistic
+ * one: z < 2^128 < r is invertible mod r, so [z][8](R + [c]A - [s]B) = O exactly when [8](R + [c]A - [s]B) = O.  Single-signature segments take
+ * the same path as every other segment.
+ * JJ_ERR_INVALID before any device work: a NULL context or base64; NULL offsets or out64 with S > 0; a NULL array with n > 0; offsets[0] != 0, a
+ * decreasing pair, or offsets in device memory; flags other than 0 or JJ_DECOMPRESS_ZIP216; 2n + S > 2^24; a misaligned device pointer ("device
+ * pointers must be 16-byte aligned").  Pointers may be host or device, mixed freely (offsets host only).
+ * VARIABLE-TIME: everything here is public.  Device work, all on the context's launch stream in a workspace the CONTEXT owns (96 bytes per term
+ * of the 2n + S, 64 per decoded point, and per signature the two ok bytes, a head slot and the copy of its two encodings): r32 | a32 copied into
+ * one region and ONE decoder launch over the 2n encodings with JJ_DECOMPRESS_CLEAR_COFACTOR, [8]B by the cofactor operation; k_sig_seg_terms
+ * (jj_sig_seg_kernels.h), one signature per lane, lays the terms out segment by segment -- segment g owns terms 2 offsets[g] + g ..: its R terms,
+ * its A terms, its own term of B -- and adds z_i s_i over the lanes of a wave that share a segment; k_sig_seg_close, one segment per lane, writes
+ * the term of B; the S sums are those of jj_msm_ragged over the term offsets 2 offsets[g] + g (segments above 8192 terms as MSM jobs, finished
+ * before the call returns); k_sig_seg_verdict writes (0, -1) over the rows of malformed segments.  Every term lies in the image of [8], so each
+ * sum is the verdict point itself and nothing is doubled afterwards; the bytes equal those of the doubled sum because an affine point has one
+ * encoding.  With a device out64 and no segment above 8192 terms the call only queues the work.
+ * Measured on an MI355X (profiles/sig_ragged_ab.txt, device-resident valid batches, signatures/s, median of five alternating rounds, every ratio outside the rounds' spread; a = one jj_sigbatch_begin job per segment, four in flight; b = the per-signature route jj_decompress x 2 + jj_point_neg + jj_fixedvar_mul_vartime_compressed, table 13): 2^20 signatures in segments of 64: 47.9 M/s (21.9 ms) against 0.137 M/s for a (350x) and 54.9 M/s for b -- 13 % BEHIND b; geometric lengths of mean 16: 37.1 M/s, 1167x a, 33 % behind b; 16 equal segments (all on the jobs route): 49.3 M/s, 1.13x a, 11 % behind b, and a third of ONE jj_sigbatch_begin job over the whole batch (140.8 M/s); segments of ONE: 9.6 M/s, 5.7x SLOWER than b (three-term sums through per-term tables against one fused ladder).  2^16: segments of 64 29.1 M/s (1.05x b), geometric 28.0 (1.03x b), 16 equal 23.6 (2.9x a, 0.87x b), segments of one 9.3 (0.34x b).  So: far ahead of a job per segment wherever segments are short, level with or behind the per-signature route everywhere, and Engine.sigbatch_locate is BEHIND it too at 2^20: 36.7 ms with one failing signature and 128.8 ms with 16 (five calls each) against 19.0 ms -- its first call alone costs more than b.  One 2^20 call in segments of 64 (kernel trace, 22.8 ms of kernels): k_msm_ragged_sum 10.8 ms, k_msm_ragged_finish 5.1 ms (nine latency-bound launches, one per round of 2^18 terms), the decoder 4.5 ms, k_msm_batch_tables 1.8 ms; the decoder's extra cofactor pass 0.54 ms (2.4 %), the three new kernels 0.12 ms. */
+int jj_sigbatch_ragged(jj_ctx*, const void* base64, size_t S, const uint64_t* offsets, const void* r32, const void* a32, const void* s32, const void* c32, const void* z16,
+                       unsigned flags, void* out64);
 
 /* ---- encodings ----------------------------------------------------------------------------------------- */
 #define JJ_DECOMPRESS_ZIP216          1u  /* reject the two non-canonical encodings (src/lib.rs:469-471, 522-531) */

@@ -444,6 +444,24 @@ inline SigVerdict sigbatch_keyed_verify(const Context& c, const Bytes64& base, c
                                         bool zip216 = false) {
   return sigbatch_verdict(sigbatch_keyed_begin(c, base, keys, offsets, R, s, ch, z, zip216)->finish());
 }
+// S batch checks over consecutive runs of one signature array, one verdict per run (jj_sigbatch_ragged): segment g holds signatures
+// offsets[g] .. offsets[g+1]; row g is what sigbatch_begin + finish give for that segment alone (an empty segment: the identity).
+inline std::vector<Bytes64> sigbatch_ragged(const Context& c, const Bytes64& base, const std::vector<uint64_t>& offsets, const std::vector<Bytes32>& R, const std::vector<Bytes32>& A,
+                                            const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z, bool zip216 = false) {
+  const size_t n = R.size();
+  if (A.size() != n || s.size() != n || ch.size() != n || z.size() != n || (!offsets.empty() && offsets.back() != n) || (offsets.empty() && n)) throw Error(JJ_ERR_INVALID, "length mismatch");
+  const size_t S = offsets.empty() ? 0 : offsets.size() - 1;
+  std::vector<Bytes64> out(S);
+  c.check(jj_sigbatch_ragged(c.raw(), base.data(), S, offsets.data(), R.data(), A.data(), s.data(), ch.data(), z.data(), zip216 ? JJ_DECOMPRESS_ZIP216 : 0u, out.data()));
+  return out;
+}
+inline std::vector<SigVerdict> sigbatch_ragged_verify(const Context& c, const Bytes64& base, const std::vector<uint64_t>& offsets, const std::vector<Bytes32>& R,
+                                                      const std::vector<Bytes32>& A, const std::vector<Bytes32>& s, const std::vector<Bytes32>& ch, const std::vector<Bytes16>& z,
+                                                      bool zip216 = false) {
+  std::vector<SigVerdict> v;
+  for (const Bytes64& row : sigbatch_ragged(c, base, offsets, R, A, s, ch, z, zip216)) v.push_back(sigbatch_verdict(row));
+  return v;
+}
 // MSM cut into parts (jj_msm_partial / jj_msm_combine): part g of G by windows (every part sees all terms) or all windows of a slice
 // of the terms; the records are combined in one host tail
 using MsmRecord = std::array<uint8_t, JJ_MSM_PARTIAL_BYTES>;

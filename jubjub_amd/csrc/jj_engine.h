@@ -216,6 +216,9 @@ struct jj_ctx {
   int msm_ragged_slice_min = 16, msm_ragged_waves = 2048, msm_ragged_round_terms = 1 << 18;
   // jj_msm_ragged's work list on its way to the device: page-locked, owned by the context; ragged_ev = the copy of the last list has read it
   uint8_t* ragged_host = nullptr; size_t ragged_host_cap = 0; hipEvent_t ragged_ev = nullptr; bool ragged_in_flight = false;
+  // jj_sigbatch_ragged's workspace (terms, decoded points, ok bytes, head slots, encodings, offsets, bad words, [8]B, staged host inputs) and the
+  // device copy of a host result; used on the context's launch stream only, which orders one call's kernels after the previous call's
+  DevBuf sigseg, sigseg_out;
   bool torsion_ladder = false;   // subgroup test: false = Tate pairing (k_torsion_free), true = multiply by r (reference definition)
   bool fb_const_time = true;     // fixed-base window select: true = lane-staged + ds_bpermute shuffle, false = per-lane LDS gather
   int fb_default_kind = 7;       // what window_bits = 0 means: 7 = signed comb (32 additions + 3 doublings), 6 = signed 6-bit windows (43 additions); JJ_FIXEDBASE_DEFAULT

@@ -3,6 +3,7 @@
 #include "jj_engine.h"
 #include "jj_sig_kernels.h"
 #include "jj_sig_keyed_kernels.h"
+#include "jj_sig_seg_kernels.h"
 
 // MSM on the device up to the record of partial window sums (jj_msm_kernels.h); everything here is launches only (the
 // workspaces are grown first), so a pass can be queued behind another one without any host synchronisation in between.
@@ -829,29 +830,21 @@ static int msm_ragged_enqueue(jj_ctx* c, size_t S, const uint64_t* off, const ui
   }
   return JJ_OK;
 }
-JJ_API int jj_msm_ragged(jj_ctx* c, size_t S, const uint64_t* offsets, const void* scalars, const void* points, void* out64) {
-  if (!c) return JJ_ERR_INVALID;
-  if (S == 0) return JJ_OK;
-  if (!offsets || !out64 || is_device_ptr(offsets) || !msm_ragged_offsets_ok(S, offsets)) return JJ_ERR_INVALID;
-  const size_t N = (size_t)offsets[S];
-  if (N && (!scalars || !points)) return JJ_ERR_INVALID;
-  JJ_ENTER(c);
+// the sums of a call on device arrays ds / dp (all N terms), after staging: the identity to the rows of empty segments, the short segments through
+// msm_ragged_enqueue, then the long ones as MSM jobs over the same arrays, a few in flight (the host tail of one beside the kernels of the next).
+// The jobs' results come back in res (64 bytes per entry of longs): the caller puts them in place, behind everything queued here.
+static int msm_ragged_locked(jj_ctx* c, size_t S, const uint64_t* offsets, const uint8_t* ds, const uint8_t* dp, uint8_t* dout, std::vector<size_t>& longs, std::vector<uint8_t>& res) {
   size_t empty = 0;
-  std::vector<size_t> longs;                            // the segments of the jobs route
+  longs.clear();                                        // the segments of the jobs route
   for (size_t s = 0; s < S; s++) { const uint64_t len = offsets[s + 1] - offsets[s]; if (!len) empty++; else if (len > MSM_BATCH_MAX) longs.push_back(s); }
-  int rc; OutRef o;
-  const void *ds = nullptr, *dp = nullptr;
-  if ((rc = stage_in(c, 0, scalars, 32 * N, &ds))) return rc;
-  if ((rc = stage_in(c, 1, points, 64 * N, &dp))) return rc;
-  if ((rc = stage_out(c, c->out[0], out64, 64 * S, &o))) return rc;
+  int rc;
   if (empty) {
     // the identity (0, 1) in every row; the finish launches and the jobs then write the rows of the non-empty segments
-    HIPCHK(c, hipMemsetAsync(o.dev, 0, S * 64, c->stream));
-    HIPCHK(c, hipMemset2DAsync((uint8_t*)o.dev + 32, 64, 1, 1, S, c->stream));
+    HIPCHK(c, hipMemsetAsync(dout, 0, S * 64, c->stream));
+    HIPCHK(c, hipMemset2DAsync(dout + 32, 64, 1, 1, S, c->stream));
   }
-  if ((rc = msm_ragged_enqueue(c, S, offsets, (const uint8_t*)ds, (const uint8_t*)dp, (uint8_t*)o.dev))) return rc;
-  // long segments: one MSM job each over the staged arrays, a few in flight (the host tail of one beside the kernels of the next)
-  std::vector<uint8_t> res(longs.size() * 64);
+  if ((rc = msm_ragged_enqueue(c, S, offsets, ds, dp, dout))) return rc;
+  res.assign(longs.size() * 64, 0);
   if (!longs.empty()) {
     const size_t depth = 2 * (size_t)std::max(1, c->msm_lanes);
     std::vector<std::pair<jj_msm_job*, size_t>> q;
@@ -860,20 +853,119 @@ JJ_API int jj_msm_ragged(jj_ctx* c, size_t S, const uint64_t* offsets, const voi
     for (size_t k = 0; k < longs.size() && !rc; k++) {
       const uint64_t lo = offsets[longs[k]], len = offsets[longs[k] + 1] - lo;
       jj_msm_job* j = nullptr;
-      const int r = msm_begin_locked(c, (size_t)len, (const uint8_t*)ds + lo * 32, (const uint8_t*)dp + lo * 64, 0, 1, true, &j);
+      const int r = msm_begin_locked(c, (size_t)len, ds + lo * 32, dp + lo * 64, 0, 1, true, &j);
       if (r) { rc = r; break; }
       q.emplace_back(j, k);
       if (q.size() - head > depth) finish_one();
     }
     while (head < q.size()) finish_one();                 // every job is finished (and released), also after a failure
-    if (rc) return rc;
-    if (!o.host) for (size_t k = 0; k < longs.size(); k++) HIPCHK(c, hipMemcpyAsync((uint8_t*)o.dev + longs[k] * 64, res.data() + 64 * k, 64, hipMemcpyHostToDevice, c->stream));
   }
+  return rc;
+}
+JJ_API int jj_msm_ragged(jj_ctx* c, size_t S, const uint64_t* offsets, const void* scalars, const void* points, void* out64) {
+  if (!c) return JJ_ERR_INVALID;
+  if (S == 0) return JJ_OK;
+  if (!offsets || !out64 || is_device_ptr(offsets) || !msm_ragged_offsets_ok(S, offsets)) return JJ_ERR_INVALID;
+  const size_t N = (size_t)offsets[S];
+  if (N && (!scalars || !points)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  int rc; OutRef o;
+  const void *ds = nullptr, *dp = nullptr;
+  if ((rc = stage_in(c, 0, scalars, 32 * N, &ds))) return rc;
+  if ((rc = stage_in(c, 1, points, 64 * N, &dp))) return rc;
+  if ((rc = stage_out(c, c->out[0], out64, 64 * S, &o))) return rc;
+  std::vector<size_t> longs;
+  std::vector<uint8_t> res;
+  if ((rc = msm_ragged_locked(c, S, offsets, (const uint8_t*)ds, (const uint8_t*)dp, (uint8_t*)o.dev, longs, res))) return rc;
+  if (!o.host) for (size_t k = 0; k < longs.size(); k++) HIPCHK(c, hipMemcpyAsync((uint8_t*)o.dev + longs[k] * 64, res.data() + 64 * k, 64, hipMemcpyHostToDevice, c->stream));
   bool sync = !longs.empty();
   if ((rc = finish_out(c, o, &sync))) return rc;
   if ((rc = finish(c, sync))) return rc;
   if (o.host) for (size_t k = 0; k < longs.size(); k++) memcpy((uint8_t*)out64 + longs[k] * 64, res.data() + 64 * k, 64);
   return JJ_OK;
+}
+// ---- S batch Schnorr checks over consecutive runs of one signature array, one verdict point per run (jj_sigbatch_ragged; kernels:
+// jj_sig_seg_kernels.h).  Segment g owns the terms 2 offsets[g] + g .. 2 offsets[g + 1] + g of ONE term array: its R terms, its A terms, its own
+// term of B; msm_ragged_locked sums every segment (an empty one is the single term [0] B).  The decoder runs ONCE over r32 | a32 with the cofactor
+// flag and [8] B comes from the cofactor operation (jj_point_mul_by_cofactor on one point), so every sum is the verdict point itself: neither
+// k_msm_ragged_finish nor jj_msm_finish doubles anything.  The sums land in device memory (the caller's rows, or c->sigseg_out for a host result),
+// the long segments' rows are copied there, k_sig_seg_verdict then writes (0, -1) over the rows of segments with a malformed unit, and a host
+// result is copied out last.  Workspace c->sigseg: points | scalars | decoded points | ok bytes | head slots | encodings | offsets | bad | B, [8] B |
+// staged host inputs; everything on the context's launch stream (the long segments' jobs are finished before the call returns).
+static bool sig_seg_offsets_ok(size_t S, const uint64_t* off, size_t* n) {
+  const uint64_t MAXT = (uint64_t)1 << 24;
+  *n = 0;
+  if (S > MAXT || off[0] != 0) return false;
+  for (size_t g = 0; g < S; g++) if (off[g + 1] < off[g]) return false;
+  if (off[S] > (MAXT - S) / 2) return false;                                   // 2n + S terms: one pass of the MSM for every segment, 32-bit term indices
+  *n = (size_t)off[S];
+  return true;
+}
+JJ_API int jj_sigbatch_ragged(jj_ctx* c, const void* base64, size_t S, const uint64_t* offsets, const void* r32, const void* a32, const void* s32, const void* c32, const void* z16,
+                              unsigned flags, void* out64) {
+  if (!c || !base64 || (flags & ~(unsigned)JJ_DECOMPRESS_ZIP216)) return JJ_ERR_INVALID;
+  if (S == 0) return JJ_OK;
+  size_t n = 0;
+  if (!offsets || !out64 || is_device_ptr(offsets) || !sig_seg_offsets_ok(S, offsets, &n)) return JJ_ERR_INVALID;
+  if (n && (!r32 || !a32 || !s32 || !c32 || !z16)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  const bool out_dev = is_device_ptr(out64);
+  if ((out_dev && ((uintptr_t)out64 & 15u)) || (is_device_ptr(base64) && ((uintptr_t)base64 & 15u))) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  if (n == 0) {                                                                // S identities; no array is read
+    if (out_dev) {
+      HIPCHK(c, hipMemsetAsync(out64, 0, S * 64, c->stream));
+      HIPCHK(c, hipMemset2DAsync((uint8_t*)out64 + 32, 64, 1, 1, S, c->stream));
+      return finish(c, false);
+    }
+    for (size_t g = 0; g < S; g++) memcpy((uint8_t*)out64 + 64 * g, AFFINE_IDENTITY_BYTES, 64);
+    return JJ_OK;
+  }
+  const size_t T = 2 * n + S;
+  const struct { const void* p; size_t elem; } arr[5] = {{r32, 32}, {a32, 32}, {s32, 32}, {c32, 32}, {z16, 16}};
+  bool dev[5];
+  for (int k = 0; k < 5; k++) {
+    dev[k] = is_device_ptr(arr[k].p);
+    if (dev[k] && ((uintptr_t)arr[k].p & 15u)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += sig_up(bytes); return o; };
+  const size_t o_pts = take(T * 64), o_scal = take(T * 32), o_dec = take(2 * n * 64), o_ok = take(2 * n), o_heads = take(n * 32), o_enc = take(2 * n * 32);
+  const size_t o_offs = take((S + 1) * 8), o_bad = take(S * 4), o_base = take(64), o_b8 = take(64);
+  size_t o_in[5] = {o_enc, o_enc + 32 * n, 0, 0, 0};                           // R and A always land in the decoder's one input region
+  for (int k = 2; k < 5; k++) o_in[k] = dev[k] ? 0 : take(n * arr[k].elem);
+  int rc; OutRef o;
+  if ((rc = ensure(c, c->sigseg, off)) || (rc = stage_out(c, c->sigseg_out, out64, 64 * S, &o))) return rc;
+  uint8_t* g = (uint8_t*)c->sigseg.p;
+  auto to_dev = [&](void* dst, const void* src, size_t bytes, bool src_dev) -> int {
+    if (!src_dev && bytes >= BOUNCE_THRESHOLD && !is_pinned_host(src, bytes)) return host_to_dev_bounced(c, dst, src, bytes);
+    if (hipMemcpyAsync(dst, src, bytes, src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_ragged: staging copy failed"; return JJ_ERR_HIP; }
+    return JJ_OK;
+  };
+  const void* in[5];
+  for (int k = 0; k < 5; k++) {
+    if (k >= 2 && dev[k]) { in[k] = arr[k].p; continue; }
+    if ((rc = to_dev(g + o_in[k], arr[k].p, n * arr[k].elem, dev[k]))) return rc;
+    in[k] = g + o_in[k];
+  }
+  if ((rc = to_dev(g + o_offs, offsets, (S + 1) * 8, false)) || (rc = to_dev(g + o_base, base64, 64, is_device_ptr(base64)))) return rc;
+  HIPCHK(c, hipMemsetAsync(g + o_bad, 0, S * 4, c->stream));
+  if ((rc = jj_point_mul_by_cofactor(c, 1, g + o_base, g + o_b8))) return rc;
+  if ((rc = decompress_dev(c, 2 * n, g + o_enc, flags | JJ_DECOMPRESS_CLEAR_COFACTOR, g + o_dec, g + o_ok, false))) return rc;
+  const unsigned long long* doffs = (const unsigned long long*)(g + o_offs);
+  hipLaunchKernelGGL(k_sig_seg_terms, dim3(blocks_for(n, SIG_THREADS)), dim3(SIG_THREADS), 0, c->stream, n, (u32)S, doffs, in[2], in[3], in[4], (const uint8_t*)(g + o_ok), (const void*)(g + o_dec),
+                     (void*)(g + o_pts), (void*)(g + o_scal), (void*)(g + o_heads), (u32*)(g + o_bad));
+  hipLaunchKernelGGL(k_sig_seg_close, dim3(blocks_for(S, SIG_THREADS)), dim3(SIG_THREADS), 0, c->stream, (u32)S, doffs, (const void*)(g + o_heads), (const void*)(g + o_b8), (void*)(g + o_pts),
+                     (void*)(g + o_scal));
+  std::vector<uint64_t> toff(S + 1);                                           // the term offsets of the S sums
+  for (size_t k = 0; k <= S; k++) toff[k] = 2 * offsets[k] + k;
+  std::vector<size_t> longs;
+  std::vector<uint8_t> res;
+  if ((rc = msm_ragged_locked(c, S, toff.data(), g + o_scal, g + o_pts, (uint8_t*)o.dev, longs, res))) return rc;
+  for (size_t k = 0; k < longs.size(); k++) HIPCHK(c, hipMemcpyAsync((uint8_t*)o.dev + longs[k] * 64, res.data() + 64 * k, 64, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_sig_seg_verdict, dim3(blocks_for(S, SIG_THREADS)), dim3(SIG_THREADS), 0, c->stream, (u32)S, (const u32*)(g + o_bad), o.dev);
+  bool sync = !longs.empty();                                                  // res leaves with this call
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
 }
 // ---- fixed-basis MSM (jj_msm_basis_*): the points are handed over once, every call brings scalars only.  A basis keeps, in the memory of its
 // device, the tables {0 .. 8} P of its first min(n, MSM_BATCH_MAX) points (rows of up to MSM_BATCH_MAX terms run through k_msm_batch_sum /

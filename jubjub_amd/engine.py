@@ -199,6 +199,81 @@ def _group_by_key(A):
     return srt[starts], np.concatenate([starts, [n]]).astype(np.uint64), order.astype(np.int64)
 
 
+def _sigbatch_ragged_args(base, offsets, R, A, s, c, z):
+    """jj_sigbatch_ragged's arguments, checked before any C call: base 64 bytes; offsets S + 1 integers (CSR, offsets[-1] = n); R, A, s, c of shape
+    (n, 32); z of shape (n, 16) or None.  -> (S, n, offsets as a host uint64 array, [_Arg of base, R, A, s, c, z])"""
+    shapes = [tuple(x.shape) if hasattr(x, "shape") else None for x in (base, R, A, s, c)]
+    if shapes[0] not in ((64,), (1, 64)):
+        raise ValueError("base: one affine point of shape (64,) expected, got %r" % (shapes[0],))
+    o = _ragged_offsets(offsets)
+    S, n = o.size - 1, int(o[-1])
+    for name, sh in zip(("R", "A", "s", "c"), shapes[1:]):
+        if sh != (n, 32):
+            raise ValueError("%s: shape (%d, 32) expected (offsets[-1] signatures), got %r" % (name, n, sh))
+    if 2 * n + S > 1 << 24:
+        raise ValueError("at most 2^24 terms per call (2n + S), got %d" % (2 * n + S))
+    if z is None:
+        z = _sigbatch_z(n)
+    elif not hasattr(z, "shape") or tuple(z.shape) != (n, 16):
+        raise ValueError("z: shape (%d, 16) expected, got %r" % (n, tuple(z.shape) if hasattr(z, "shape") else None))
+    return S, n, o, [_Arg(x, w) for x, w in zip((base, R, A, s, c, z), (64, 32, 32, 32, 32, 16))]
+
+
+def _sigbatch_verdicts(rows):
+    """(S, 64) verdict points (numpy or torch) -> a list of "ok" | "reject" | "malformed" """
+    if _is_torch(rows):
+        rows = rows.cpu().numpy()
+    out = []
+    for row in np.asarray(rows, np.uint8).reshape(-1, 64):
+        b = row.tobytes()
+        out.append("ok" if b == SIGBATCH_IDENTITY else "malformed" if b == SIGBATCH_MALFORMED else "reject")
+    return out
+
+
+def _locate_cut(lo, hi, fanout):
+    """[lo, hi) cut into min(fanout, hi - lo) consecutive non-empty parts whose lengths differ by at most one: the list of their bounds"""
+    k = min(fanout, hi - lo)
+    base, rem = divmod(hi - lo, k)
+    bounds = [lo]
+    for j in range(k):
+        bounds.append(bounds[-1] + base + (1 if j < rem else 0))
+    return bounds
+
+
+def _sigbatch_locate(n, fanout, verdicts_of):
+    """The bisection of Engine.sigbatch_locate over a verdict function: verdicts_of(index, offsets) -> one verdict string per segment of the gathered
+    units (index None: all n units in their order; else the list of units to gather).  Pure Python; tests/test_sig_seg_cases_cpu.py runs it over
+    the oracle."""
+    fanout = int(fanout)
+    if fanout < 2:
+        raise ValueError("fanout: at least 2 expected, got %r" % (fanout,))
+    if n == 0:
+        return []
+    found = []
+    segs = [(0, n)]                                      # the failing segments of the round before, as ranges of the caller's indices
+    first = True
+    while segs:
+        index, offsets, parts = [], [0], []
+        for lo, hi in segs:
+            b = _locate_cut(lo, hi, fanout)
+            for p0, p1 in zip(b[:-1], b[1:]):
+                parts.append((p0, p1))
+                offsets.append(offsets[-1] + p1 - p0)
+                if not first:
+                    index.extend(range(p0, p1))
+        verdicts = verdicts_of(None if first else index, offsets)
+        first = False
+        segs = []
+        for (p0, p1), v in zip(parts, verdicts):
+            if v == "ok":
+                continue
+            if p1 - p0 == 1:
+                found.append((p0, v))
+            else:
+                segs.append((p0, p1))
+    return sorted(found)
+
+
 SIGBATCH_IDENTITY = bytes(32) + bytes([1]) + bytes(31)
 SIGBATCH_MALFORMED = bytes(32) + (0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001 - 1).to_bytes(32, "little")
 
@@ -801,6 +876,53 @@ class Engine:
         """sigbatch_keyed_begin + msm_finish -> "ok" | "reject" | "malformed" """
         out = self.msm_finish(self.sigbatch_keyed_begin(base, keys, offsets, R, s, c, z, zip216)).tobytes()
         return "ok" if out == SIGBATCH_IDENTITY else "malformed" if out == SIGBATCH_MALFORMED else "reject"
+
+    def sigbatch_ragged(self, base, offsets, R, A, s, c, z=None, zip216=False, out=None):
+        """S batch checks over consecutive runs of one signature array in one call (jj_sigbatch_ragged): segment g holds signatures
+        offsets[g] .. offsets[g+1] (offsets: S + 1 integers, kept on the host, offsets[0] = 0, non-decreasing, offsets[-1] = n).  R, A, s, c (n, 32),
+        z (n, 16) -- drawn from `secrets`, every z_i non-zero, when None -- and base (64,): numpy arrays or torch CUDA tensors, mixed freely.
+        Returns (S, 64) of R's kind: row g is byte for byte what sigbatch_begin + msm_finish give for segment g alone -- (0, 1) accept (also an empty
+        segment), (0, -1) a malformed unit in that segment, any other point a failing signature.  A segment of one signature is an exact cofactored
+        check of it.  `out`: a caller-owned (S, 64) array of R's kind.  VARIABLE-TIME; everything here is public."""
+        S, n, o, args = _sigbatch_ragged_args(base, offsets, R, A, s, c, z)
+        like = args[1]
+        if out is None:
+            out, optr = self._alloc(like, S, 64)
+        else:
+            oa = _Arg(out, 64)
+            if oa.n != S or oa.torch != like.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x 64 bytes of R's kind expected" % S)
+            optr = oa.ptr
+        self._bind_stream(args)
+        self._check(self._lib.jj_sigbatch_ragged(self._ctx, args[0].ptr, C.c_size_t(S), o.ctypes.data, *[a.ptr for a in args[1:]], C.c_uint(FLAG_ZIP216 if zip216 else 0), optr))
+        return out
+
+    def sigbatch_ragged_verify(self, base, offsets, R, A, s, c, z=None, zip216=False):
+        """sigbatch_ragged -> a list of "ok" | "reject" | "malformed", one per segment"""
+        return _sigbatch_verdicts(self.sigbatch_ragged(base, offsets, R, A, s, c, z, zip216))
+
+    def sigbatch_locate(self, base, R, A, s, c, z=None, zip216=False, fanout=16):
+        """The signatures of a batch that fail on their own: the sorted list of (index, "reject" | "malformed").  Bisection with sigbatch_ragged: the
+        whole batch as `fanout` segments first; each following round gathers only the units of the segments that are not "ok", cuts each such
+        segment into up to `fanout` parts and repeats until the failing segments hold one signature (an exact check of it).  A valid batch costs
+        one call, a batch with failures at most 1 + ceil(log_fanout(n)) calls.  Two failing signatures in one segment hide each other -- their terms
+        cancel in the weighted sum -- with chance 2^-128 per round; a malformed unit never hides.  z: (n, 16) weights, drawn once when None and
+        gathered with their signatures."""
+        n = int(R.shape[0])
+        arrays = [R, A, s, c, _sigbatch_z(n) if z is None else z]
+
+        def gather(x, index):
+            if _is_torch(x):
+                import torch
+
+                return x[torch.as_tensor(index, dtype=torch.long, device=x.device)]
+            return np.asarray(x)[np.asarray(index, dtype=np.int64)]
+
+        def verdicts_of(index, offsets):
+            sub = arrays if index is None else [gather(x, index) for x in arrays]
+            return self.sigbatch_ragged_verify(base, offsets, *sub, zip216=zip216)
+
+        return _sigbatch_locate(n, fanout, verdicts_of)
 
     def msm_finish(self, job):
         """-> the 64-byte affine sum as a numpy array (host memory)."""

@@ -223,6 +223,19 @@ impl Gpu {
         assert_eq!(unsafe { jj_sigbatch_keyed_begin(self.0, b.as_ptr() as _, keys.len(), keys.as_ptr() as _, offsets.as_ptr(), r.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, z.as_ptr() as _, if zip216 { 1 } else { 0 }, &mut job) }, 0);
         MsmJob { job, _keep: (b, ss) }                      // host arrays and the offsets are staged at begin
     }
+    /// One batch check per run of one signature array (`jj_sigbatch_ragged`): segment `g` holds signatures `offsets[g] .. offsets[g+1]`
+    /// (`offsets[0] = 0`, non-decreasing, the last one `n`); row `g` is the point `sigbatch_begin` + `msm_finish` give for that segment alone:
+    /// the identity to accept (also an empty segment), `(0, -1)` for a malformed unit in it, any other point a failing signature.
+    /// Variable-time; everything is public.
+    pub fn sigbatch_ragged(&self, base: &AffinePoint, offsets: &[u64], r: &[[u8; 32]], a: &[[u8; 32]], s: &[Fr], c: &[[u8; 32]], z: &[[u8; 16]], zip216: bool) -> Vec<AffinePoint> {
+        let n = r.len();
+        if offsets.is_empty() { assert_eq!(n, 0); return Vec::new(); }
+        assert!(*offsets.last().unwrap() as usize == n && a.len() == n && s.len() == n && c.len() == n && z.len() == n);
+        let (rows, b, ss) = (offsets.len() - 1, put_points(std::slice::from_ref(base)), put_scalars(s));
+        let mut out = vec![0u8; 64 * rows];
+        assert_eq!(unsafe { jj_sigbatch_ragged(self.0, b.as_ptr() as _, rows, offsets.as_ptr(), r.as_ptr() as _, a.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, z.as_ptr() as _, if zip216 { 1 } else { 0 }, out.as_mut_ptr() as _) }, 0);
+        out.chunks_exact(64).map(get_point).collect()
+    }
     pub fn msm_finish(&self, j: MsmJob) -> AffinePoint {
         let mut out = [0u8; 64];
         assert_eq!(unsafe { jj_msm_finish(j.job, out.as_mut_ptr() as _) }, 0);
