@@ -578,7 +578,48 @@ int jj_sigbatch_keyed_begin(jj_ctx*, const void* base64, size_t K, const void* a
 int jj_sigbatch_ragged(jj_ctx*, const void* base64, size_t S, const uint64_t* offsets, const void* r32, const void* a32, const void* s32, const void* c32, const void* z16,
                        unsigned flags, void* out64);
 
-/* ---- encodings ----------------------------------------------------------------------------------------- */
+/* ---- one Schnorr verdict PER SIGNATURE, in one synchronous call: what a verifier asks once a batch is rejected, or when it has no batch.
+ *   t         a table of jj_fixedbase_table_create for the base B, any window_bits.  A composite table: JJ_ERR_INVALID.
+ *   r32 a32   encodings of R_i and A_i;  s32: s_i canonical, s_i >= r is malformed;  c32: any 256-bit integer, reduced mod r here
+ *             (n x 32 each, as in jj_sigbatch_begin)
+ *   flags     a subset of JJ_DECOMPRESS_ZIP216 (the decoder's rule for R and A) | JJ_SIG_COFACTORLESS; anything else: JJ_ERR_INVALID
+ *             before any device work
+ *   verdict   n bytes:  JJ_SIG_MALFORMED  R_i or A_i does not decode, or s_i >= r
+ *                       JJ_SIG_OK         otherwise, iff [8]([s_i]B - [c_i mod r]A_i - R_i) = O -- the COFACTORED equation of every jj_sigbatch_*
+ *                                         call; with JJ_SIG_COFACTORLESS iff [s_i]B - [c_i mod r]A_i - R_i = O (the three doublings left out:
+ *                                         what comparing encodings checks)
+ *                       JJ_SIG_REJECT     otherwise
+ *             Nothing else is written for a unit.
+ * VARIABLE-TIME: digit-dependent table addresses in both terms.  Everything here is public (signatures, keys, challenges).
+ * Pointers may be host or device, mixed freely (device pointers 16-byte aligned).  n = 0 succeeds, touches nothing, and the arrays may be
+ * NULL.  JJ_ERR_INVALID: a NULL context or table, a NULL array with n > 0, a table of another device.  Synchronous under the context lock and
+ * the stream rules of jj_fixedvar_mul_vartime (a device verdict array is written in launch-stream order).  n is processed in chunks of 2^20
+ * units queued one after another; the context-owned workspace (162 bytes per unit and the ladder's own) is bounded by the chunk, not by n.
+ * Kernels: k_decompress twice per chunk (R, then A: the caller's arrays are not contiguous; through jj_decompress one launch over 2^21 encodings
+ * with the copy that makes them so takes 3.64 ms against 3.84 ms for two calls over 2^20, a difference below the 0.24 ms the second CALL costs
+ * by itself, which two launches inside one entry point do not pay), k_sig_each_prep (c mod r, s < r, -A in place, the identity over a failed
+ * decode, the MALFORMED bytes), the ladders of jj_fixedvar_mul_vartime by its own rule for the table and the size, and k_sig_each_tail on the
+ * three coordinates they leave: R subtracted as an affine-Niels operand, three doublings, Curve::is_identity, ONE byte stored -- no k_normalize,
+ * no compress, no jj_point_neg pass, no compare in the caller.  Bounds: the tail adds to the output of an addition and doubles the output of an
+ * addition, both in the set tools/bounds_check.py check_curve iterates over (jj_sig_each.h).
+ * Measured on an MI355X (profiles/sig_each_ab.txt: device-resident valid batches, five alternating rounds of one process per route, median; the
+ * composed route -- jj_decompress x 2 + jj_point_neg + jj_fixedvar_mul_vartime_compressed + the caller's compare -- on a build of the parent
+ * commit): 2^20 signatures, table 13: 18.25 ms per call cofactored (57.5 M signatures/s), 18.08 ms cofactorless, against 18.58 ms for the composed
+ * route, which checks the cofactorless rule -- 1.018x and 1.028x, both outside the rounds' spread; table 10: 18.38 / 18.28 against 18.77 ms.  2^16:
+ * 2.26 / 2.25 against 2.41 ms (1.07x); 2^10: 0.942 / 0.936 against 1.055 ms (1.12x: three calls fewer).  So the gain is what was supposed, a few
+ * percent, and no more: one 2^20 call is k_varbase_fixed 14.9 ms, the decoder 2 x 2.23 ms, k_sig_each_tail 0.22 ms, k_sig_each_prep 0.04 ms
+ * (kernel trace).  A fused kernel that kept the ladder's accumulator in registers for the tail (k_sig_each) was built and measured: level at 2^10
+ * and 2^16, 2.3 % and 2.2 % SLOWER at 2^20 (tables 13, 10), beyond the spread; it is not in the library (experiments/sig_each_fused).
+ * Engine.sig_locate (one jj_sigbatch_begin job, then this call only if the batch is rejected) at 2^20: 7.1 ms for a valid batch against 21.3 ms
+ * for Engine.sigbatch_locate and 18.5 ms for the composed route; 26.0 ms with 1 or with 16 failing signatures against 36.8 / 150.3 ms for
+ * sigbatch_locate -- and BEHIND the composed route or this call alone (18.6 / 18.3 ms) whenever the batch fails: the batch job is then paid on top. */
+#define JJ_SIG_REJECT       0u
+#define JJ_SIG_OK           1u
+#define JJ_SIG_MALFORMED    2u
+#define JJ_SIG_COFACTORLESS 16u  /* flag of jj_sigverify_each; clear of the JJ_DECOMPRESS_* bits */
+int jj_sigverify_each(jj_ctx*, const jj_table* t, size_t n, const void* r32, const void* a32, const void* s32, const void* c32, unsigned flags, uint8_t* verdict);
+
+/* ---- encodings----------------------------------------------------------------------------------------- */
 #define JJ_DECOMPRESS_ZIP216          1u  /* reject the two non-canonical encodings (src/lib.rs:469-471, 522-531) */
 #define JJ_DECOMPRESS_TORSION_FREE    2u  /* additionally require [r]P = O  (SubgroupPoint::from_bytes, lib.rs:1427-1429) */
 #define JJ_DECOMPRESS_NOT_SMALL_ORDER 4u  /* additionally reject small-order points (lib.rs:699-705) */

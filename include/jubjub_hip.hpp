@@ -462,6 +462,18 @@ inline std::vector<SigVerdict> sigbatch_ragged_verify(const Context& c, const By
   for (const Bytes64& row : sigbatch_ragged(c, base, offsets, R, A, s, ch, z, zip216)) v.push_back(sigbatch_verdict(row));
   return v;
 }
+// One verdict per signature in one call (jj_sigverify_each): JJ_SIG_OK iff [8]([s]B - [c]A - R) = O, B the base of `g` -- the cofactored equation
+// of every sigbatch_* call; cofactored = false: iff [s]B - [c]A - R = O --, JJ_SIG_MALFORMED for an R or A that does not decode or s >= r, else
+// JJ_SIG_REJECT.  Variable-time; everything is public.
+inline std::vector<uint8_t> sigverify_each(const FixedBase& g, const std::vector<Bytes32>& R, const std::vector<Bytes32>& A, const std::vector<Bytes32>& s,
+                                           const std::vector<Bytes32>& ch, bool zip216 = false, bool cofactored = true) {
+  const size_t n = R.size();
+  if (A.size() != n || s.size() != n || ch.size() != n) throw Error(JJ_ERR_INVALID, "length mismatch");
+  const Context& c = g.context();
+  std::vector<uint8_t> v(n);
+  c.check(jj_sigverify_each(c.raw(), g.raw(), n, R.data(), A.data(), s.data(), ch.data(), (zip216 ? JJ_DECOMPRESS_ZIP216 : 0u) | (cofactored ? 0u : JJ_SIG_COFACTORLESS), v.data()));
+  return v;
+}
 // MSM cut into parts (jj_msm_partial / jj_msm_combine): part g of G by windows (every part sees all terms) or all windows of a slice
 // of the terms; the records are combined in one host tail
 using MsmRecord = std::array<uint8_t, JJ_MSM_PARTIAL_BYTES>;

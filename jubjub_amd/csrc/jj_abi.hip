@@ -684,6 +684,57 @@ JJ_API int jj_decompress(jj_ctx* c, size_t n, const void* in32, unsigned flags, 
     return decompress_dev(c, cn, din[0], flags, dout[0], (uint8_t*)dout[1], staged);
   });
 }
+// ---- one Schnorr verdict per signature (kernels: beside k_varbase_fixed in jj_kernels.h, jj_sig_each.h): verdict[i] = OK iff
+// [8]([s_i]B - [c_i mod r]A_i - R_i) = O, without the three doublings under JJ_SIG_COFACTORLESS; MALFORMED for an undecodable R_i or A_i and
+// for s_i >= r.  VARIABLE-TIME.  Per chunk of SIG_EACH_CHUNK units, queued one after another on the launch stream: the decoder twice (R, then A:
+// the caller's two arrays are not contiguous, and one launch over both needs a copy of 64 bytes per unit first; measured through jj_decompress,
+// one launch over 2^21 with that copy takes 3.64 ms against 3.84 ms for two calls over 2^20 -- 0.20 ms, less than the 0.24 ms the second CALL
+// costs by itself at 2^10, which two launches inside one entry point do not pay: two launches), k_sig_each_prep, fixedvar_to_ext unchanged --
+// every table kind and size by its own rule: k_varbase_fixed, or a ladder and the table's kernel -- on (s, c mod r, -A), then k_sig_each_tail
+// on the coordinates it leaves: R subtracted as an affine-Niels operand, three doublings, the identity test, one byte stored.  No
+// k_normalize, no compress, no jj_point_neg pass, no compare in the caller.  The workspace (c->sigeach: 64 + 64 + 2 + 32 bytes per unit of a
+// chunk, and the ladders' own) is bounded by the chunk; host arrays are staged whole by the front end like every entry point's.
+// A fused k_sig_each (the ladder of k_varbase_fixed with the tail in registers: 196 VGPRs, no scratch, no coordinate stored) was built and
+// measured against this route: level at 2^10 and 2^16 units, 2.3 % BEHIND at 2^20 with table 13 (18.67 against 18.25 ms) and 2.2 % with table
+// 10 (18.78 against 18.38 ms), both beyond the spread of the rounds (1 % in an earlier session) -- the tail's 30 products run at two waves per
+// SIMD there; here k_sig_each_tail takes 0.22 ms per 2^20 units at full occupancy.  It was removed (experiments/sig_each_fused holds it as a
+// patch; profiles/sig_each_ab.txt the runs).
+constexpr size_t SIG_EACH_CHUNK = (size_t)1 << 20;      // units per chunk
+static_assert(SIG_EACH_REJECT == JJ_SIG_REJECT && SIG_EACH_OK == JJ_SIG_OK && SIG_EACH_MALFORMED == JJ_SIG_MALFORMED, "verdict bytes of jj_sig_each.h and jubjub_hip.h");
+static_assert((JJ_SIG_COFACTORLESS & (JJ_DECOMPRESS_ZIP216 | JJ_DECOMPRESS_TORSION_FREE | JJ_DECOMPRESS_NOT_SMALL_ORDER | JJ_DECOMPRESS_CLEAR_COFACTOR)) == 0, "JJ_SIG_COFACTORLESS shares a bit with a decoder flag");
+static size_t sig_each_up(size_t x) { return (x + 255) & ~(size_t)255; }
+static int sig_each_chunk(jj_ctx* c, const jj_table* t, size_t n, const void* dr, const void* da, const void* ds, const void* dc, unsigned flags, uint8_t* dverdict) {
+  int rc;
+  uint8_t* g = (uint8_t*)c->sigeach.p;
+  uint8_t* const pts = g; uint8_t* const ok = pts + sig_each_up(128 * n); uint8_t* const cp = ok + sig_each_up(2 * n);
+  const unsigned dflags = flags & JJ_DECOMPRESS_ZIP216;
+  const int cofactored = (flags & JJ_SIG_COFACTORLESS) ? 0 : 1;
+  if ((rc = decompress_dev(c, n, dr, dflags, pts, ok, false))) return rc;
+  if ((rc = decompress_dev(c, n, da, dflags, pts + 64 * n, ok + n, false))) return rc;
+  hipLaunchKernelGGL(k_sig_each_prep, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, dc, ok, (void*)pts, (void*)cp, dverdict);
+  if ((rc = ensure_ext(c, n, 5))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  if ((rc = fixedvar_to_ext(c, t, n, ds, cp, pts + 64 * n, ext))) return rc;
+  hipLaunchKernelGGL(k_sig_each_tail, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ext, (const void*)pts, (const uint8_t*)ok, dverdict, cofactored);
+  return JJ_OK;
+}
+JJ_API int jj_sigverify_each(jj_ctx* c, const jj_table* t, size_t n, const void* r32, const void* a32, const void* s32, const void* c32, unsigned flags, uint8_t* verdict) {
+  if (!c || !t) return JJ_ERR_INVALID;
+  if (n && (!r32 || !a32 || !s32 || !c32 || !verdict)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (flags & ~(unsigned)(JJ_DECOMPRESS_ZIP216 | JJ_SIG_COFACTORLESS)) { c->err = "jj_sigverify_each: flags other than the ZIP-216 bit (1) and the cofactorless bit (16)"; return JJ_ERR_INVALID; }
+  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_sigverify_each needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
+  return run_batch(c, n, {{r32, 32, 0}, {a32, 32, 1}, {s32, 32, 2}, {c32, 32, 3}}, {{verdict, 1, &c->okb}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    const size_t ch = std::min(n, SIG_EACH_CHUNK);
+    int rc = ensure(c, c->sigeach, sig_each_up(128 * ch) + sig_each_up(2 * ch) + 32 * ch); if (rc) return rc;
+    for (size_t lo = 0; lo < n; lo += SIG_EACH_CHUNK) {
+      const size_t cn = std::min(SIG_EACH_CHUNK, n - lo);
+      if ((rc = sig_each_chunk(c, t, cn, (const uint8_t*)din[0] + 32 * lo, (const uint8_t*)din[1] + 32 * lo, (const uint8_t*)din[2] + 32 * lo, (const uint8_t*)din[3] + 32 * lo, flags, (uint8_t*)dout[0] + lo))) return rc;
+    }
+    return JJ_OK;
+  });
+}
 JJ_API int jj_batch_normalize(jj_ctx* c, size_t n, const void* ext160, void* out64) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);

@@ -219,6 +219,8 @@ struct jj_ctx {
   // jj_sigbatch_ragged's workspace (terms, decoded points, ok bytes, head slots, encodings, offsets, bad words, [8]B, staged host inputs) and the
   // device copy of a host result; used on the context's launch stream only, which orders one call's kernels after the previous call's
   DevBuf sigseg, sigseg_out;
+  // jj_sigverify_each's workspace of ONE chunk (decoded R | -A, ok bytes, reduced challenges); launch stream only, like sigseg
+  DevBuf sigeach;
   bool torsion_ladder = false;   // subgroup test: false = Tate pairing (k_torsion_free), true = multiply by r (reference definition)
   bool fb_const_time = true;     // fixed-base window select: true = lane-staged + ds_bpermute shuffle, false = per-lane LDS gather
   int fb_default_kind = 7;       // what window_bits = 0 means: 7 = signed comb (32 additions + 3 doublings), 6 = signed 6-bit windows (43 additions); JJ_FIXEDBASE_DEFAULT

@@ -1100,6 +1100,46 @@ __global__ void __launch_bounds__(256, JJ_VB_MINWAVES) k_varbase_fixed(size_t n,
   }
 }
 #endif  // JJ_KERNELS_BATCH
+// One Schnorr verdict per signature (jj_sigverify_each, jj_sig_each.h).  k_decompress has left R_i and A_i in slots [0, n) and [n, 2n) of
+// `points` and their ok bytes in ok[0, n) and ok[n, 2n); k_sig_each_prep readies a unit for the ladders of fixedvar_to_ext; k_sig_each_tail runs
+// SigEach::tail on the three coordinates they leave.  A verdict leaves as one byte store per lane; nothing else is written for a unit.
+// (A k_sig_each that kept the accumulator of k_varbase_fixed in registers for the tail measured 2 % SLOWER than these two kernels at 2^20 units
+// and was taken out again: experiments/sig_each_fused, profiles/sig_each_ab.txt.)
+}  // namespace jj
+#include "jj_sig_each.h"
+namespace jj {
+#ifdef JJ_KERNELS_BATCH
+// per unit: cprime = c mod r (canonical), ok[i] = R, A decoded and s < r, A := -A, the identity over a failed decode, MALFORMED where it applies
+__global__ void __launch_bounds__(256) k_sig_each_prep(size_t n, const void* s32, const void* c32, uint8_t* ok, void* points, void* cprime, uint8_t* verdict) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 w[8];
+  load8(w, c32, i);
+  SigEach<VB_W>::challenge(w);
+  store8(cprime, i, w);
+  load8(w, s32, i);
+  const bool s_ok = SigEach<VB_W>::scalar_ok(w);
+  const bool r_ok = ok[i] != 0, a_ok = ok[n + i] != 0;
+  // a failed decode left (0, 0), which is not on the curve: the ladder runs on the identity instead
+  u32 id_u[8], id_v[8];
+  zero8(id_u); zero8(id_v); id_v[0] = 1;
+  if (!r_ok) { store8(points, 2 * i, id_u); store8(points, 2 * i + 1, id_v); }
+  if (!a_ok) { store8(points, 2 * (n + i), id_u); store8(points, 2 * (n + i) + 1, id_v); }
+  else { load8(w, points, 2 * (n + i)); SigEach<VB_W>::neg_u(w); store8(points, 2 * (n + i), w); }
+  const bool good = r_ok && a_ok && s_ok;
+  ok[i] = good ? 1 : 0;
+  if (!good) verdict[i] = (uint8_t)SIG_EACH_MALFORMED;
+}
+// SigEach::tail on the coordinates 0..2 that fixedvar_to_ext left in `ext`; ok: the merged byte of k_sig_each_prep (a malformed unit keeps its verdict)
+__global__ void __launch_bounds__(256) k_sig_each_tail(size_t n, SoA ext, const void* r, const uint8_t* ok, uint8_t* verdict, int cofactored) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (!ok[i]) return;
+  const Ext acc = SigEach<VB_W>::from_uvz(ext.get(0, i), ext.get(1, i), ext.get(2, i));
+  const bool good = SigEach<VB_W>::tail(acc, load_affine(r, i), cofactored != 0);
+  verdict[i] = (uint8_t)(good ? SIG_EACH_OK : SIG_EACH_REJECT);
+}
+#endif  // JJ_KERNELS_BATCH
 // affine points (64 B canonical) -> table entries (AffineNiels limbs, 112 B)
 #ifdef JJ_KERNELS_BATCH
 __global__ void __launch_bounds__(256) k_affine_to_table(size_t n, const void* pts, u32* table, int stride) {

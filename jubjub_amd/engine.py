@@ -17,6 +17,8 @@ FLAG_ZIP216 = 1
 FLAG_TORSION_FREE = 2
 FLAG_NOT_SMALL_ORDER = 4
 FLAG_CLEAR_COFACTOR = 8
+FLAG_SIG_COFACTORLESS = 16     # jj_sigverify_each only
+SIG_REJECT, SIG_OK, SIG_MALFORMED = 0, 1, 2      # verdict bytes of jj_sigverify_each
 
 
 class JubjubError(RuntimeError):
@@ -907,7 +909,7 @@ class Engine:
         segment into up to `fanout` parts and repeats until the failing segments hold one signature (an exact check of it).  A valid batch costs
         one call, a batch with failures at most 1 + ceil(log_fanout(n)) calls.  Two failing signatures in one segment hide each other -- their terms
         cancel in the weighted sum -- with chance 2^-128 per round; a malformed unit never hides.  z: (n, 16) weights, drawn once when None and
-        gathered with their signatures."""
+        gathered with their signatures.  sig_locate answers the same question with one batch job and, for a rejected batch, one sigverify_each."""
         n = int(R.shape[0])
         arrays = [R, A, s, c, _sigbatch_z(n) if z is None else z]
 
@@ -923,6 +925,45 @@ class Engine:
             return self.sigbatch_ragged_verify(base, offsets, *sub, zip216=zip216)
 
         return _sigbatch_locate(n, fanout, verdicts_of)
+
+    def sigverify_each(self, table, R, A, s, c, zip216=False, cofactored=True, out=None):
+        """One verdict per signature in one call (jj_sigverify_each): table a fixedbase_table of the base B (any window_bits, not a composite
+        one); R, A compressed points, s responses, c challenges (n, 32; c is reduced mod r): numpy arrays or torch CUDA tensors, mixed freely.
+        Returns n bytes of R's kind: SIG_OK (1) iff [8]([s]B - [c]A - R) = O -- the cofactored equation of every sigbatch_* call; with
+        cofactored=False iff [s]B - [c]A - R = O, what comparing encodings checks --, SIG_MALFORMED (2) for an R or A that does not decode
+        (zip216: the decoder's rule) or s >= r, else SIG_REJECT (0).  `out`: a caller-owned array of n bytes of R's kind.  VARIABLE-TIME;
+        everything here is public."""
+        shapes = [tuple(x.shape) if hasattr(x, "shape") else None for x in (R, A, s, c)]
+        if shapes[0] is None or len(shapes[0]) != 2 or shapes[0][1] != 32:
+            raise ValueError("R: shape (n, 32) expected, got %r" % (shapes[0],))
+        n = shapes[0][0]
+        for name, sh in zip(("A", "s", "c"), shapes[1:]):
+            if sh != (n, 32):
+                raise ValueError("%s: shape (%d, 32) expected, got %r" % (name, n, sh))
+        args = [_Arg(x, 32) for x in (R, A, s, c)]
+        like = args[0]
+        if out is None:
+            out, optr = self._alloc(like, n, 1)
+        else:
+            oa = _Arg(out, 1)
+            if oa.n != n or oa.torch != like.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d bytes of R's kind expected" % n)
+            optr = oa.ptr
+        self._bind_stream(args)
+        flags = (FLAG_ZIP216 if zip216 else 0) | (0 if cofactored else FLAG_SIG_COFACTORLESS)
+        self._check(self._lib.jj_sigverify_each(self._ctx, table._h, C.c_size_t(n), *[a.ptr for a in args], C.c_uint(flags), optr))
+        return out
+
+    def sig_locate(self, base, table, R, A, s, c, z=None, zip216=False):
+        """The signatures of a batch that fail on their own, in sigbatch_locate's list format: one sigbatch_begin + msm_finish over the whole
+        batch first; "ok" returns []; otherwise ONE sigverify_each (cofactored, the batch's own equation) gives every signature its verdict and
+        the sorted list of (index, "reject" | "malformed") is returned.  table: a fixedbase_table of `base`.  Two calls at most, whatever
+        the number of failures; a rejected batch whose signatures all pass on their own (chance 2^-128 of the opposite kind) gives []."""
+        if self.sigbatch_verify(base, R, A, s, c, z, zip216) == "ok":
+            return []
+        v = self.sigverify_each(table, R, A, s, c, zip216=zip216, cofactored=True)
+        v = v.cpu().numpy() if _is_torch(v) else np.asarray(v)
+        return [(int(i), "malformed" if v[i] == SIG_MALFORMED else "reject") for i in np.nonzero(v != SIG_OK)[0]]
 
     def msm_finish(self, job):
         """-> the 64-byte affine sum as a numpy array (host memory)."""

@@ -236,6 +236,18 @@ impl Gpu {
         assert_eq!(unsafe { jj_sigbatch_ragged(self.0, b.as_ptr() as _, rows, offsets.as_ptr(), r.as_ptr() as _, a.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, z.as_ptr() as _, if zip216 { 1 } else { 0 }, out.as_mut_ptr() as _) }, 0);
         out.chunks_exact(64).map(get_point).collect()
     }
+    /// One verdict per signature in one call (`jj_sigverify_each`): `1` iff `[8]([s]B - [c]A - R) = O`, `B` the base of `g` -- the cofactored
+    /// equation of every `sigbatch_*` call; `cofactored = false`: iff `[s]B - [c]A - R = O` --, `2` for an `R` or `A` that does not decode,
+    /// else `0` (`s` is an `Fr`, so it is in range).  Variable-time; everything is public.
+    pub fn sigverify_each(&self, g: &FixedBase, r: &[[u8; 32]], a: &[[u8; 32]], s: &[Fr], c: &[[u8; 32]], zip216: bool, cofactored: bool) -> Vec<u8> {
+        let n = r.len();
+        assert!(a.len() == n && s.len() == n && c.len() == n);
+        let ss = put_scalars(s);
+        let mut out = vec![0u8; n];
+        let flags = (if zip216 { 1 } else { 0 }) | (if cofactored { 0 } else { 16 });
+        assert_eq!(unsafe { jj_sigverify_each(self.0, g.t, n, r.as_ptr() as _, a.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, flags, out.as_mut_ptr()) }, 0);
+        out
+    }
     pub fn msm_finish(&self, j: MsmJob) -> AffinePoint {
         let mut out = [0u8; 64];
         assert_eq!(unsafe { jj_msm_finish(j.job, out.as_mut_ptr() as _) }, 0);

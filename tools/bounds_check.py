@@ -377,6 +377,14 @@ def check_kernel_formulas(verbose=True):
         na_ = ops["to_niels_aff"](dict(u=ld, v=ld))
         r1, _ = lanes([(F.sub(pt["v"], pt["u"]), na_["vmu"]), (F.add(pt["v"], pt["u"]), na_["vpu"]), (Tcls, na_["t2d"])], "quad_add_aniels.r1")
         quad_finish(r1[0], r1[1], r1[2], F.add(pt["z"], pt["z"]), "quad_add_aniels.r2")
+    # ---- jj_sigverify_each (jj_sig_each.h).  SigEach::tail on k_sig_each's accumulator is add-after-add, dbl-after-add and dbl-after-dbl: the fixed
+    # point of check_curve.  SigEach::from_uvz (k_sig_each_tail) rebuilds an accumulator from three stored coordinates: (u z, v z, z z) with
+    # t1 = u, t2 = v (products) -- it must meet add_signed<T1_SMALL> with an affine-Niels operand and land back in the accumulator class
+    na_ = ops["to_niels_aff"](dict(u=ld, v=ld))
+    for pt in (inv, stored):
+        e = dict(u=F.mul(pt["u"], pt["z"], "sig_each.uz"), v=F.mul(pt["v"], pt["z"], "sig_each.vz"), z=F.sqr(pt["z"], "sig_each.zz"), t1=pt["u"], t2=pt["v"])
+        closed(e, "sig_each.from_uvz")
+        closed(ops["add_signed"](e, na_, "sig_each.tail", affine=True, small=True), "sig_each.tail")
     if verbose:
         print("  kernel formulas (normalise, decode, sqrt, pairing, quad ops): ok")
 
