@@ -500,7 +500,7 @@ int jj_msm_allgather_begin(jj_ctx*, size_t n, const void* scalars32, const void*
  *   base64   the affine base point B: any on-curve point, also one with a cofactor component (the library knows no particular generator)
  *   r32 a32  n compressed encodings each: the signature's R and the verification key A
  *   s32      n response scalars (canonical: s_i >= r is malformed)
- *   c32      n challenges as raw 32-byte integers, reduced mod r here (the caller hashes; the library knows no hash)
+ *   c32      n challenges as raw 32-byte integers, reduced mod r here (jj_sig_challenge hashes them on the device; a caller with another hash supplies its own)
  *   z16      n x 16 bytes of the caller's randomness, one 128-bit weight per signature (the library has no RNG; use non-zero weights)
  *   flags    0 or JJ_DECOMPRESS_ZIP216 (the decoder's rule for R and A)
  * Reducing the scalars mod r is exact because the cofactor is cleared at the end: [8][x]P = [x mod r][8]P for every P on the curve.
@@ -618,6 +618,54 @@ int jj_sigbatch_ragged(jj_ctx*, const void* base64, size_t S, const uint64_t* of
 #define JJ_SIG_MALFORMED    2u
 #define JJ_SIG_COFACTORLESS 16u  /* flag of jj_sigverify_each; clear of the JJ_DECOMPRESS_* bits */
 int jj_sigverify_each(jj_ctx*, const jj_table* t, size_t n, const void* r32, const void* a32, const void* s32, const void* c32, unsigned flags, uint8_t* verdict);
+
+/* ---- the challenges of the signature family, hashed on the device:
+ *   c32[i] = Fr::from_bytes_wide(BLAKE2b-512(personal16; r32[i] || a32[i] || M_i))   as 32 canonical little-endian bytes
+ * -- what every Schnorr scheme on Jubjub that the jj_sigbatch_* calls and jj_sigverify_each serve computes before the check (RedJubjub: the
+ * personalisation "Zcash_RedJubjubH").  The library still knows no protocol: the personalisation is the caller's, as the base point is.
+ * BLAKE2b as in RFC 7693: unkeyed, 64-byte digest, zero salt.
+ *   personal16  16 bytes in HOST memory, read before the call returns; NULL = sixteen zero bytes (plain BLAKE2b-512)
+ *   r32 a32     n x 32 bytes each, hashed as given (nothing is decoded).  Either may be NULL: that part is then left out of the hash; with
+ *               both NULL the call is hash-to-scalar of the messages alone
+ *   msgs        offsets == NULL: M_i is the msg_len bytes at msgs + i * msg_len (msg_len may be 0, msgs may then be NULL)
+ *               offsets != NULL: n + 1 values in HOST memory, CSR as in jj_msm_ragged (offsets[0] = 0, non-decreasing); M_i is bytes
+ *               offsets[i] .. offsets[i + 1] of msgs, msg_len must be 0.  The offsets are read before the call returns (copied to a workspace
+ *               the context owns)
+ *   c32         n x 32 bytes
+ * Pointers may be host or device, mixed freely (offsets and personal16 host only; device pointers must be 16-byte aligned at their BASE --
+ * a message inside msgs may start at any byte).  n = 0 succeeds and touches nothing.
+ * JJ_ERR_INVALID, before any device work and with c32 untouched: a NULL context; NULL c32 with n > 0; NULL msgs with a non-zero total length;
+ * offsets together with msg_len != 0; offsets[0] != 0 or a decreasing pair; offsets in device memory; n > 2^24; more than 2^32 message bytes
+ * in all; a misaligned device pointer.
+ * Synchronous in the sense of jj_sigverify_each: under the context lock, on the launch stream; a device c32 is written in launch-stream order.
+ * NOTHING has to happen between this call with a device c32 and a jj_sigbatch_begin / _keyed_begin / jj_sigbatch_ragged / jj_sigverify_each
+ * call that reads it: those calls read their challenges in kernels on the launch stream (k_sig_terms, k_sig_keyed_terms, k_sig_seg_terms,
+ * k_sig_each_prep), and the MSM lanes start a job behind everything queued there.
+ * Kernel: k_sig_challenge<parts> (jj_kernels.h, jj_blake2b.h), ONE launch over all n, one unit per lane, 256 lanes per workgroup, no workspace
+ * beyond the offsets' copy (host arrays are staged like every entry point's).  The state, the 16 message words and the working vector stay in
+ * registers: 96 VGPRs (five waves per SIMD), no scratch; one compression is 1962 vector instructions (576 64-bit adds as v_lshl_add_u64, 804
+ * v_xor_b32, 576 v_alignbit_b32 for the rotations by 24, 16 and 63; the rotation by 32 is a rename).  A message is read as aligned dwords
+ * through a funnel shift, only dwords that hold one of its bytes, so it may start anywhere; in a wave with messages of different lengths the
+ * lanes whose message has ended neither compress nor load.  One lane per message is the shape for SHORT messages (a 32- or 64-byte sighash):
+ * a kilobyte message serialises eight compressions and more in one lane and reads with a stride of its length across the wave -- the 1 KiB
+ * row below.
+ * Measured on an MI355X (profiles/sig_challenge_ab.txt: device-resident inputs and result, three alternating rounds of one process per route,
+ * median; the old route -- a hashlib.blake2b loop and jj_fr_from_bytes_wide -- on a build of the parent commit):
+ *     2^20 units, fixed stride   32-byte messages (one block with R and A)   0.084 ms per call (12.4 G challenges/s)   k_sig_challenge 0.098 ms traced
+ *                                64-byte messages (128 bytes: ONE block)     0.083 ms                                  0.093 ms
+ *                                96-byte messages (two blocks)               0.150 ms                                  0.171 ms
+ *     2^16 units                 32 / 64 / 96 bytes                          0.012 / 0.012 / 0.016 ms                  0.011 / 0.011 / 0.017 ms
+ *     2^10 units                 32 / 64 / 96 bytes                          0.012 / 0.012 / 0.016 ms (the launch)
+ *     ragged (lengths L/2 .. 3L/2)  2^20: 0.84 ms per CALL for every L, of which the kernel is 0.10 (L = 32) to 0.17 ms (L = 96): the rest is the
+ *                                8 MB of host offsets checked and copied; 2^16: 0.062 ms; 2^10: 0.019 ms
+ *     2^16 units, 1 KiB messages 0.050 ms fixed stride (nine blocks per lane: 0.095 ns per block, the rate of the one-block rows), 0.103 ms ragged
+ *     a caller's loop at 2^20 x 32 bytes: one thread 910 ms (10 800 x the call), 16 processes 101 ms (1 200 x), 113 ms with the copies of
+ *     device-resident arrays to the host and of the digests back
+ *     hash + check at 2^20, old (16 processes) against new: with jj_sigbatch_begin + jj_msm_finish 122.9 -> 7.24 ms (17.0 x), with
+ *     jj_sigverify_each 134.0 -> 18.02 ms (7.4 x): the hash now costs 1 % of the check it feeds.
+ * The estimate made before the kernel existed -- 2 500 lane-instructions per block, near 0.1 ms for 2^20 one-block challenges -- holds: 2 538 by
+ * that count (1962 issued, a 64-bit add being one instruction here), and the wide reduction's 486 v_mad_i64_i32 on top. */
+int jj_sig_challenge(jj_ctx*, size_t n, const void* personal16, const void* r32, const void* a32, const void* msgs, size_t msg_len, const uint64_t* offsets, void* c32);
 
 /* ---- encodings----------------------------------------------------------------------------------------- */
 #define JJ_DECOMPRESS_ZIP216          1u  /* reject the two non-canonical encodings (src/lib.rs:469-471, 522-531) */

@@ -474,6 +474,22 @@ inline std::vector<uint8_t> sigverify_each(const FixedBase& g, const std::vector
   c.check(jj_sigverify_each(c.raw(), g.raw(), n, R.data(), A.data(), s.data(), ch.data(), (zip216 ? JJ_DECOMPRESS_ZIP216 : 0u) | (cofactored ? 0u : JJ_SIG_COFACTORLESS), v.data()));
   return v;
 }
+// The challenges of the signature family, hashed on the device (jj_sig_challenge): c_i = Fr::from_bytes_wide(BLAKE2b-512(personal; R_i || A_i || M_i))
+// as canonical bytes.  An EMPTY R or A leaves that part out of the hash; personal == nullptr is sixteen zero bytes (RedJubjub: "Zcash_RedJubjubH").
+// The messages are packed here and may differ in length; meant for short ones (one lane hashes one message).
+inline std::vector<Bytes32> sig_challenge(const Context& c, const std::vector<Bytes32>& R, const std::vector<Bytes32>& A, const std::vector<std::vector<uint8_t>>& msgs,
+                                          const std::array<uint8_t, 16>* personal = nullptr) {
+  const size_t n = msgs.size();
+  if ((!R.empty() && R.size() != n) || (!A.empty() && A.size() != n)) throw Error(JJ_ERR_INVALID, "length mismatch");
+  std::vector<uint64_t> offsets(n + 1, 0);
+  for (size_t i = 0; i < n; i++) offsets[i + 1] = offsets[i] + msgs[i].size();
+  std::vector<uint8_t> flat;
+  flat.reserve((size_t)offsets[n]);
+  for (const auto& m : msgs) flat.insert(flat.end(), m.begin(), m.end());
+  std::vector<Bytes32> out(n);
+  c.check(jj_sig_challenge(c.raw(), n, personal ? personal->data() : nullptr, R.empty() ? nullptr : R.data(), A.empty() ? nullptr : A.data(), flat.data(), 0, offsets.data(), out.data()));
+  return out;
+}
 // MSM cut into parts (jj_msm_partial / jj_msm_combine): part g of G by windows (every part sees all terms) or all windows of a slice
 // of the terms; the records are combined in one host tail
 using MsmRecord = std::array<uint8_t, JJ_MSM_PARTIAL_BYTES>;

@@ -58,6 +58,7 @@ _SIGS.update({
     "jj_sigbatch_keyed_begin": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint, C.POINTER(_vp)],
     "jj_sigbatch_ragged": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint, _vp],
     "jj_sigverify_each": [_vp, _sz, _vp, _vp, _vp, _vp, C.c_uint, _vp],
+    "jj_sig_challenge": [_sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
     "jj_msm_partial": [_sz, _vp, _vp, C.c_int, C.c_int, _vp],
     "jj_msm_combine_dev": [_sz, _vp, _vp],
     "jj_ctx_set_comm": [_vp, C.c_int, C.c_int, _vp],

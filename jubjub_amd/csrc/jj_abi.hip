@@ -735,6 +735,48 @@ JJ_API int jj_sigverify_each(jj_ctx* c, const jj_table* t, size_t n, const void*
     return JJ_OK;
   });
 }
+// ---- Schnorr challenges hashed on the device (kernel: k_sig_challenge beside the jj_sigverify_each kernels in jj_kernels.h; jj_blake2b.h):
+// c32[i] = Fr::from_bytes_wide(BLAKE2b-512(personal16; r32[i] || a32[i] || M_i)).  Every argument is checked before anything is staged or
+// launched; the arrays then go through the staging front end (stage_in / stage_out: a device pointer passes through, a host array is copied on
+// the launch stream), the offsets through slot 3 of the same staging buffers -- the context's workspace for them --, and ONE launch over all n
+// units follows, instantiated for the number of parts.  A device c32 is written in launch-stream order; k_sig_terms, k_sig_keyed_terms,
+// k_sig_seg_terms and k_sig_each_prep read their challenges on that stream, so a jj_sigbatch_* job or jj_sigverify_each may follow at once.
+constexpr uint64_t SIG_CHALLENGE_MAX_BYTES = (uint64_t)1 << 32;     // message bytes of one call: a lane addresses them with 32 bits
+JJ_API int jj_sig_challenge(jj_ctx* c, size_t n, const void* personal16, const void* r32, const void* a32, const void* msgs, size_t msg_len, const uint64_t* offsets, void* c32) {
+  if (!c) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (n > ((size_t)1 << 24) || !c32 || (offsets && msg_len)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  uint64_t total;
+  if (offsets) {
+    if (is_device_ptr(offsets)) { c->err = "jj_sig_challenge: offsets must be in host memory"; return JJ_ERR_INVALID; }
+    if (offsets[0] != 0) { c->err = "jj_sig_challenge: offsets[0] must be 0"; return JJ_ERR_INVALID; }
+    for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) { c->err = "jj_sig_challenge: offsets must be non-decreasing"; return JJ_ERR_INVALID; }
+    total = offsets[n];
+  } else {
+    if ((uint64_t)msg_len > SIG_CHALLENGE_MAX_BYTES) { c->err = "jj_sig_challenge: more than 2^32 message bytes in one call"; return JJ_ERR_INVALID; }
+    total = (uint64_t)n * msg_len;
+  }
+  if (total > SIG_CHALLENGE_MAX_BYTES) { c->err = "jj_sig_challenge: more than 2^32 message bytes in one call"; return JJ_ERR_INVALID; }
+  if (total && !msgs) { c->err = "jj_sig_challenge: NULL msgs with message bytes to hash"; return JJ_ERR_INVALID; }
+  for (const void* p : {r32, a32, total ? msgs : nullptr, (const void*)c32})
+    if (p && ((uintptr_t)p & 15u) && is_device_ptr(p)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  uint64_t personal[2] = {0, 0};
+  if (personal16) memcpy(personal, personal16, 16);
+  int rc;
+  const void *dr, *da, *dm, *doff;
+  OutRef o;
+  if ((rc = stage_in(c, 0, r32, r32 ? 32 * n : 0, &dr)) || (rc = stage_in(c, 1, a32, a32 ? 32 * n : 0, &da)) || (rc = stage_in(c, 2, msgs, (size_t)total, &dm)) ||
+      (rc = stage_in(c, 3, offsets, offsets ? 8 * (n + 1) : 0, &doff)) || (rc = stage_out(c, c->out[0], c32, 32 * n, &o))) return rc;
+  const void* p0 = dr ? dr : da;
+  const dim3 grid(blocks_for(n)), block(256);
+  if (dr && da) hipLaunchKernelGGL(k_sig_challenge<2>, grid, block, 0, c->stream, n, (u64)personal[0], (u64)personal[1], dr, da, (const uint8_t*)dm, (u64)msg_len, (const unsigned long long*)doff, o.dev);
+  else if (p0) hipLaunchKernelGGL(k_sig_challenge<1>, grid, block, 0, c->stream, n, (u64)personal[0], (u64)personal[1], p0, (const void*)nullptr, (const uint8_t*)dm, (u64)msg_len, (const unsigned long long*)doff, o.dev);
+  else hipLaunchKernelGGL(k_sig_challenge<0>, grid, block, 0, c->stream, n, (u64)personal[0], (u64)personal[1], (const void*)nullptr, (const void*)nullptr, (const uint8_t*)dm, (u64)msg_len, (const unsigned long long*)doff, o.dev);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
 JJ_API int jj_batch_normalize(jj_ctx* c, size_t n, const void* ext160, void* out64) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);

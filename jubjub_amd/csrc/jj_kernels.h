@@ -1140,6 +1140,32 @@ __global__ void __launch_bounds__(256) k_sig_each_tail(size_t n, SoA ext, const 
   verdict[i] = (uint8_t)(good ? SIG_EACH_OK : SIG_EACH_REJECT);
 }
 #endif  // JJ_KERNELS_BATCH
+// Schnorr challenges hashed on the device (jj_sig_challenge, jj_blake2b.h): c32[i] = Fr::from_bytes_wide(BLAKE2b-512(personal; parts || M_i)) as
+// 32 canonical bytes, one unit per lane.  PARTS 32-byte parts (p0, then p1) precede the message; M_i is msg_len bytes at msgs + i * msg_len,
+// or bytes offsets[i] .. offsets[i + 1] of msgs when offsets (a DEVICE copy) is given.  The digest goes through the functions behind
+// jj_fr_from_bytes_wide (Fr::from_words_wide, Fr::to_words) without leaving the registers.  Every byte offset of an existing message byte is
+// below 2^32 (the entry point bounds the bytes of a call), so a lane addresses msgs with 32 bits beside the uniform base.
+}  // namespace jj
+#include "jj_blake2b.h"
+namespace jj {
+#ifdef JJ_KERNELS_BATCH
+template <int PARTS>
+__global__ void __launch_bounds__(256) k_sig_challenge(size_t n, u64 personal_lo, u64 personal_hi, const void* p0, const void* p1, const uint8_t* msgs, u64 msg_len,
+                                                       const unsigned long long* offsets, void* c32) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 a[8], b[8];
+  if constexpr (PARTS >= 1) load8(a, p0, i); else zero8(a);
+  if constexpr (PARTS >= 2) load8(b, p1, i); else zero8(b);
+  u64 len = msg_len; u32 pos = (u32)((u64)i * msg_len);
+  if (offsets) { const u64 o = offsets[i]; len = offsets[i + 1] - o; pos = (u32)o; }
+  u32 lo[8], hi[8];
+  Blake2b::hash<PARTS>(lo, hi, personal_lo, personal_hi, a, b, msgs, pos, len);
+  u32 w[8];
+  Fr::to_words(w, Fr::from_words_wide(lo, hi));
+  store8(c32, i, w);
+}
+#endif  // JJ_KERNELS_BATCH
 // affine points (64 B canonical) -> table entries (AffineNiels limbs, 112 B)
 #ifdef JJ_KERNELS_BATCH
 __global__ void __launch_bounds__(256) k_affine_to_table(size_t n, const void* pts, u32* table, int stride) {

@@ -19,6 +19,7 @@ FLAG_NOT_SMALL_ORDER = 4
 FLAG_CLEAR_COFACTOR = 8
 FLAG_SIG_COFACTORLESS = 16     # jj_sigverify_each only
 SIG_REJECT, SIG_OK, SIG_MALFORMED = 0, 1, 2      # verdict bytes of jj_sigverify_each
+REDJUBJUB_PERSONAL = b"Zcash_RedJubjubH"         # the personalisation of RedJubjub's challenge hash: the documented example of sig_challenge's `personal` (the C library does not contain it)
 
 
 class JubjubError(RuntimeError):
@@ -964,6 +965,67 @@ class Engine:
         v = self.sigverify_each(table, R, A, s, c, zip216=zip216, cofactored=True)
         v = v.cpu().numpy() if _is_torch(v) else np.asarray(v)
         return [(int(i), "malformed" if v[i] == SIG_MALFORMED else "reject") for i in np.nonzero(v != SIG_OK)[0]]
+
+    def sig_challenge(self, R, A, msgs, personal=None, offsets=None, out=None):
+        """The challenges of the signature family, hashed on the device (jj_sig_challenge):
+        c_i = Fr::from_bytes_wide(BLAKE2b-512(personal; R_i || A_i || M_i)) as (n, 32) canonical bytes.  R, A: (n, 32) arrays, hashed as given;
+        either may be None and is then left out of the hash (both None: hash-to-scalar of the messages alone).  msgs: an (n, L) uint8 array or
+        CUDA tensor (every message L bytes), a flat uint8 array or tensor with `offsets` (n + 1 integers, CSR: message i is bytes
+        offsets[i] .. offsets[i + 1]), or a list of bytes objects, which is packed here.  personal: 16 bytes (REDJUBJUB_PERSONAL is RedJubjub's)
+        or None for sixteen zero bytes.  numpy arrays or torch CUDA tensors, mixed freely; the result is of R's kind when R is given, else of
+        msgs' kind, or `out`.  A device result may be handed straight to sigbatch_begin, sigbatch_verify or sigverify_each: they read it on
+        the same stream.  Meant for SHORT messages (one lane hashes one message)."""
+        if personal is not None:
+            personal = bytes(personal)
+            if len(personal) != 16:
+                raise ValueError("personal: 16 bytes expected, got %d" % len(personal))
+        if isinstance(msgs, (list, tuple)) and all(isinstance(m, (bytes, bytearray, memoryview)) for m in msgs):
+            if offsets is not None:
+                raise ValueError("offsets: not with a list of messages (it is packed here)")
+            offsets = np.zeros(len(msgs) + 1, np.uint64)
+            offsets[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+            msgs = np.frombuffer(b"".join(bytes(m) for m in msgs), dtype=np.uint8)
+        shape = tuple(msgs.shape) if hasattr(msgs, "shape") else None
+        if offsets is None:
+            if shape is None or len(shape) != 2:
+                raise ValueError("msgs: shape (n, L), a flat array with offsets, or a list of bytes expected, got %r" % (shape,))
+            n, msg_len, optr_off = shape[0], shape[1], None
+        else:
+            if shape is None or len(shape) != 1:
+                raise ValueError("msgs: a flat uint8 array expected beside offsets, got %r" % (shape,))
+            offsets = _ragged_offsets(offsets)
+            if int(offsets[-1]) != shape[0]:
+                raise ValueError("offsets[-1] = %d, but msgs holds %d bytes" % (int(offsets[-1]), shape[0]))
+            n, msg_len, optr_off = offsets.size - 1, 0, offsets.ctypes.data
+        if n > 1 << 24:
+            raise ValueError("at most 2^24 challenges per call, got %d" % n)
+        if n * msg_len > 1 << 32 or (offsets is not None and int(offsets[-1]) > 1 << 32):
+            raise ValueError("at most 2^32 message bytes per call")
+        for name, x in (("R", R), ("A", A)):
+            if x is not None and (not hasattr(x, "shape") or tuple(x.shape) != (n, 32)):
+                raise ValueError("%s: shape (%d, 32) or None expected, got %r" % (name, n, tuple(x.shape) if hasattr(x, "shape") else None))
+        ra, aa, ma = (None if R is None else _Arg(R, 32)), (None if A is None else _Arg(A, 32)), _Arg(msgs, None)
+        like = ra if ra is not None else ma
+        if out is None:
+            out, optr = self._alloc(like, n, 32)
+        else:
+            oa = _Arg(out, 32)
+            if oa.n != n or oa.torch != like.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x 32 bytes of %s kind expected" % (n, "R's" if ra is not None else "msgs'"))
+            optr = oa.ptr
+        self._bind_stream([a for a in (ra, aa, ma) if a is not None] + [like])
+        self._check(self._lib.jj_sig_challenge(self._ctx, C.c_size_t(n), personal, ra.ptr if ra else None, aa.ptr if aa else None, ma.ptr, C.c_size_t(msg_len), optr_off, optr))
+        return out
+
+    def sigverify_each_msgs(self, table, R, A, s, msgs, personal, offsets=None, zip216=False, cofactored=True, out=None):
+        """sig_challenge(R, A, msgs, personal, offsets), then sigverify_each with those challenges: one verdict byte per signature from the
+        messages themselves.  With R on the device the challenges never visit the host."""
+        return self.sigverify_each(table, R, A, s, self.sig_challenge(R, A, msgs, personal, offsets), zip216=zip216, cofactored=cofactored, out=out)
+
+    def sigbatch_verify_msgs(self, base, R, A, s, msgs, personal, offsets=None, z=None, zip216=False):
+        """sig_challenge(R, A, msgs, personal, offsets), then sigbatch_verify with those challenges -> "ok" | "reject" | "malformed".  With R on
+        the device the challenges never visit the host."""
+        return self.sigbatch_verify(base, R, A, s, self.sig_challenge(R, A, msgs, personal, offsets), z, zip216)
 
     def msm_finish(self, job):
         """-> the 64-byte affine sum as a numpy array (host memory)."""

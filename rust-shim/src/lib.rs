@@ -248,6 +248,20 @@ impl Gpu {
         assert_eq!(unsafe { jj_sigverify_each(self.0, g.t, n, r.as_ptr() as _, a.as_ptr() as _, ss.as_ptr() as _, c.as_ptr() as _, flags, out.as_mut_ptr()) }, 0);
         out
     }
+    /// The challenges of the signature family, hashed on the device (`jj_sig_challenge`):
+    /// `c_i = Fr::from_bytes_wide(BLAKE2b-512(personal; r_i || a_i || msgs[i]))` as canonical bytes.  `r` / `a`: `None` leaves that part out of the
+    /// hash; `personal`: `None` is sixteen zero bytes (RedJubjub: `b"Zcash_RedJubjubH"`).  The messages are packed here and may differ in length.
+    pub fn sig_challenge(&self, personal: Option<&[u8; 16]>, r: Option<&[[u8; 32]]>, a: Option<&[[u8; 32]]>, msgs: &[&[u8]]) -> Vec<[u8; 32]> {
+        let n = msgs.len();
+        assert!(r.map_or(true, |x| x.len() == n) && a.map_or(true, |x| x.len() == n));
+        let mut offsets = vec![0u64; n + 1];
+        for (i, m) in msgs.iter().enumerate() { offsets[i + 1] = offsets[i] + m.len() as u64; }
+        let flat: Vec<u8> = msgs.concat();
+        let mut out = vec![[0u8; 32]; n];
+        let ptr = |x: Option<&[[u8; 32]]>| x.map_or(std::ptr::null(), |v| v.as_ptr() as *const c_void);
+        assert_eq!(unsafe { jj_sig_challenge(self.0, n, personal.map_or(std::ptr::null(), |p| p.as_ptr() as *const c_void), ptr(r), ptr(a), flat.as_ptr() as _, 0, offsets.as_ptr(), out.as_mut_ptr() as _) }, 0);
+        out
+    }
     pub fn msm_finish(&self, j: MsmJob) -> AffinePoint {
         let mut out = [0u8; 64];
         assert_eq!(unsafe { jj_msm_finish(j.job, out.as_mut_ptr() as _) }, 0);
