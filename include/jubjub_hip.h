@@ -667,6 +667,52 @@ int jj_sigverify_each(jj_ctx*, const jj_table* t, size_t n, const void* r32, con
  * that count (1962 issued, a 64-bit add being one instruction here), and the wide reduction's 486 v_mad_i64_i32 on top. */
 int jj_sig_challenge(jj_ctx*, size_t n, const void* personal16, const void* r32, const void* a32, const void* msgs, size_t msg_len, const uint64_t* offsets, void* c32);
 
+/* ---- windowed Pedersen hashes: one launch for n units, every segment in one accumulator.  VARIABLE-TIME (public inputs): the table address
+ * depends on the message; a caller with secret inputs composes jj_pedersen_scalars with jj_fixedbase_multi_mul on the LDS tables.
+ * A message M is `prefix_bits` bits of `prefix` (low bits first), then up to four fields of the unit's row; every bit is taken LSB-first within
+ * its byte.  M is padded with zero bits to a multiple of 3 and cut into chunks (s0, s1, s2) in message order,
+ *     enc = (1 - 2 s2)(1 + s0 + 2 s1)  in +-{1..4};   segment j takes chunks j c .. j c + c - 1, c = seg_chunks (the last takes what is left);
+ *     <M_j> = sum_i enc(m_i) 16^i   (|<M_j>| <= 4 (16^63 - 1) / 15 < (r - 1) / 2);        H(M) = sum_j [<M_j>] P_j.
+ * The empty message gives the identity; a chunk that is not there contributes nothing (it is not a zero chunk: 000 encodes +1).  The library
+ * knows no protocol: generators, chunks per segment and prefix are the caller's (for the hash of the Zcash protocol specification section
+ * 5.4.1.7: seg_chunks = 63, its generators; a Merkle layer over a buffer of node u-coordinates is ONE call with rows = the nodes, row_stride
+ * = 64, fields = {0, 255, 32, 255}, prefix = the layer number, prefix_bits = 6, and its 32-byte output rows are the next layer's rows of 64).
+ * jj_pedersen_table_create
+ *   nseg 1..8, seg_chunks 1..63, window_chunks 1..4 or 0 = the default (4)
+ *   gens64   nseg affine points, host or device; each must be on the curve and torsion-free, else JJ_ERR_INVALID -- the integer sum and the
+ *            sum over scalars reduced mod r are then the same point
+ *   The table holds, per segment and window of w = window_chunks chunks (windows never straddle a segment; the last is shorter), sub-tables for
+ *   t = 1 .. w present chunks of 2^(3t - 1) entries, 128 bytes each (layout: jj_pedersen.h): 4 + 32 + 256 + 2048 entries per window at w = 4,
+ *   106 176 entries = 13.6 MB for three segments of 63.  Built by jj_varbase_mul on host-made scalars and k_affine_to_table; freed by
+ *   jj_fixedbase_table_destroy.  Every other entry point that takes a jj_table refuses a Pedersen table with JJ_ERR_INVALID.
+ * jj_pedersen_hash_vartime
+ *   fields   HOST array of 2 * nfields values (byte_offset, nbits), nfields 0..4: field f of unit i is nbits bits from byte
+ *            rows + i * row_stride + byte_offset; nbits >= 1, byte_offset + ceil(nbits / 8) <= row_stride; fields may overlap
+ *   rows     host or device (16-byte aligned); n * row_stride <= 2^32; may be NULL when nfields = 0
+ *   the message (prefix_bits + sum nbits, ONE length per call) must fit 3 * seg_chunks * nseg bits
+ *   flags    0: out is n x 32 bytes, the canonical u-coordinate;  JJ_PEDERSEN_POINT: n x 64 affine bytes
+ *   JJ_ERR_INVALID before anything is staged or launched, out untouched: a table that is not a Pedersen table, prefix_bits outside 0..32, nfields
+ *   outside 0..4, a field past row_stride, a message over capacity, unknown flags, a misaligned device pointer.  n = 0 succeeds and touches nothing.
+ *   Kernel k_pedersen_gather (jj_kernels.h): one unit per lane, the walk of k_fixedbase_gather with the message's own bits as the digit; the
+ *   per-window plan (which bytes, what shift, where a field ends -- the same for every unit) is made on the host and read with uniform
+ *   addresses; rows are read as aligned dwords through a funnel shift, never beyond the last dword that holds a covered byte of the lane's own
+ *   row.  Then the shared normaliser, and k_affine_u for the u-only form.  139 VGPRs, no scratch.
+ *   Measured on an MI355X (profiles/pedersen_ab.txt: rows and results on the device, three alternating rounds of one process per route, median):
+ *   2^20 hashes of the Merkle shape (516 bits, 44 additions) 2.097 ms per call at window_chunks 4 (500 M hashes/s; 2.68 ms at 3, 3.97 ms at 2),
+ *   against 2.496 ms for jj_pedersen_scalars + jj_fixedbase_multi_mul over three 16-bit gathered tables (201 MB), 5.56 ms over the default LDS
+ *   tables, and 2128 ms for a caller that encodes the scalars in numpy; 2^16: 0.219 ms; 2^10: 0.211 ms (44 dependent additions).  The 576-bit
+ *   one-field shape (four segments): 2.364 against 3.294 ms.
+ * jj_pedersen_scalars
+ *   writes <M_j> mod r as canonical Fr bytes, (nseg, n, 32) -- the layout jj_fixedbase_multi_mul reads; a segment the message does not reach
+ *   gets 0.  The composed device route and the cross-check of the fused kernel: jj_fixedbase_multi_mul over these scalars with tables of the
+ *   same generators gives the bytes of jj_pedersen_hash_vartime(JJ_PEDERSEN_POINT).  Kernel k_pedersen_scalars, one (unit, segment) per lane. */
+#define JJ_PEDERSEN_POINT 1u
+int jj_pedersen_table_create(jj_ctx*, int nseg, const void* gens64, int seg_chunks, int window_chunks /* 0 = default */, jj_table** out);
+int jj_pedersen_hash_vartime(jj_ctx*, const jj_table* t, size_t n, unsigned prefix, int prefix_bits,
+                             const void* rows, size_t row_stride, int nfields, const uint32_t* fields, unsigned flags, void* out);
+int jj_pedersen_scalars(jj_ctx*, int nseg, int seg_chunks, size_t n, unsigned prefix, int prefix_bits,
+                        const void* rows, size_t row_stride, int nfields, const uint32_t* fields, void* scalars32);
+
 /* ---- encodings----------------------------------------------------------------------------------------- */
 #define JJ_DECOMPRESS_ZIP216          1u  /* reject the two non-canonical encodings (src/lib.rs:469-471, 522-531) */
 #define JJ_DECOMPRESS_TORSION_FREE    2u  /* additionally require [r]P = O  (SubgroupPoint::from_bytes, lib.rs:1427-1429) */

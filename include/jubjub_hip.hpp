@@ -276,6 +276,45 @@ inline AffineBatch fixedbase_multi_mul(const std::vector<const FixedBase*>& base
   return AffineBatch(c, std::move(out));
 }
 
+// Windowed Pedersen hashes (jj_pedersen_*; the function and its arguments: jubjub_hip.h).  The table of `gens` (each on the curve and
+// torsion-free), seg_chunks chunks per generator; hash(): one message per row of `rows` -- `prefix_bits` bits of `prefix`, then the fields
+// (byte_offset, nbits) of the row -- as the canonical u-coordinate.  VARIABLE-TIME: public inputs.  A Merkle layer over node u-coordinates is
+// hash(nodes, 64, {{0, 255}, {32, 255}}, layer, 6).
+class PedersenTable {
+ public:
+  PedersenTable(const Context& c, const std::vector<Bytes64>& gens, int seg_chunks = 63, int window_chunks = 0) : c_(&c), nseg_((int)gens.size()), seg_chunks_(seg_chunks) {
+    c.check(jj_pedersen_table_create(c.raw(), nseg_, gens.data(), seg_chunks, window_chunks, &t_));
+  }
+  ~PedersenTable() { if (t_) jj_fixedbase_table_destroy(c_->raw(), t_); }
+  PedersenTable(const PedersenTable&) = delete;
+  PedersenTable& operator=(const PedersenTable&) = delete;
+  std::vector<Bytes32> hash(const std::vector<uint8_t>& rows, size_t row_stride, const std::vector<std::array<uint32_t, 2>>& fields, unsigned prefix = 0, int prefix_bits = 0) const {
+    const size_t n = row_stride ? rows.size() / row_stride : 0;
+    std::vector<Bytes32> out(n);
+    c_->check(jj_pedersen_hash_vartime(c_->raw(), t_, n, prefix, prefix_bits, rows.data(), row_stride, (int)fields.size(), fields.empty() ? nullptr : fields[0].data(), 0, out.data()));
+    return out;
+  }
+  AffineBatch hash_points(const std::vector<uint8_t>& rows, size_t row_stride, const std::vector<std::array<uint32_t, 2>>& fields, unsigned prefix = 0, int prefix_bits = 0) const {
+    const size_t n = row_stride ? rows.size() / row_stride : 0;
+    std::vector<Bytes64> out(n);
+    c_->check(jj_pedersen_hash_vartime(c_->raw(), t_, n, prefix, prefix_bits, rows.data(), row_stride, (int)fields.size(), fields.empty() ? nullptr : fields[0].data(), JJ_PEDERSEN_POINT, out.data()));
+    return AffineBatch(*c_, std::move(out));
+  }
+  // <M_j> mod r, segment-major (nseg x n): what fixedbase_multi_mul reads -- the route for secret inputs, over the constant-time LDS tables
+  std::vector<Bytes32> scalars(const std::vector<uint8_t>& rows, size_t row_stride, const std::vector<std::array<uint32_t, 2>>& fields, unsigned prefix = 0, int prefix_bits = 0) const {
+    const size_t n = row_stride ? rows.size() / row_stride : 0;
+    std::vector<Bytes32> out(n * (size_t)nseg_);
+    c_->check(jj_pedersen_scalars(c_->raw(), nseg_, seg_chunks_, n, prefix, prefix_bits, rows.data(), row_stride, (int)fields.size(), fields.empty() ? nullptr : fields[0].data(), out.data()));
+    return out;
+  }
+  const jj_table* raw() const { return t_; }
+
+ private:
+  const Context* c_;
+  int nseg_, seg_chunks_;
+  jj_table* t_ = nullptr;
+};
+
 // batch_normalize (lib.rs:1084-1107): (U,V,Z,T1,T2) canonical 160-byte records -> affine
 inline AffineBatch batch_normalize(const Context& c, const std::vector<std::array<uint8_t, 160>>& ext) {
   std::vector<Bytes64> out(ext.size());

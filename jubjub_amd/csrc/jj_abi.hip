@@ -471,6 +471,7 @@ static int fixedbase_api(jj_ctx* c, const jj_table* t, size_t n, const void* sca
   if (!c || !t) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; }
   // lanes of the table's kernel: one workgroup per CU for the LDS tables, fb_gather_blocks_per_cu blocks of 256 for the gathered ones
   const size_t fb_lanes = t->window_bits == 7 ? (size_t)c->cus * FBC_THREADS : t->window_bits == FB_W ? (size_t)c->cus * FB_THREADS : (size_t)c->cus * c->fb_gather_blocks_per_cu * 256;
   return run_to_points(c, n, {{scalars, 32, 0}}, out, mode, 3, pipe_chunk_for(c, n, 20, fb_lanes), fb_lanes, [&](size_t cn, const void* const* din, SoA ext) -> int {
@@ -485,6 +486,7 @@ JJ_API int jj_fixedbase_multi_mul(jj_ctx* c, const jj_table* const* tables, int 
   for (int j = 0; j < nbases; j++) if (!tables[j]) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   for (int j = 0; j < nbases; j++) if (tables[j]->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  for (int j = 0; j < nbases; j++) { const jj_table* t = tables[j]; if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; } }
   return run_to_points(c, n, {{scalars, 32 * (size_t)nbases, 0}}, out64, 0, 5, 0, 0, [&](size_t n, const void* const* din, SoA ext) -> int {
     for (int j = 0; j < nbases; j++) {
       const int chain = (j > 0 ? 1 : 0) | (j + 1 < nbases ? 2 : 0);
@@ -574,6 +576,7 @@ static int fixedvar_api(jj_ctx* c, const jj_table* t, size_t n, const void* a, c
   if (n && (!a || !b || !q || !out)) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; }
   if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_fixedvar_mul_vartime needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
   return run_to_points(c, n, {{a, 32, 0}, {b, 32, 2}, {q, 64, 3}}, out, mode, 5, pipe_chunk_for(c, n, 18), 0, [&](size_t cn, const void* const* din, SoA ext) -> int {      // (the table stays resident)
     return fixedvar_to_ext(c, t, cn, din[0], din[1], din[2], ext);
@@ -724,6 +727,7 @@ JJ_API int jj_sigverify_each(jj_ctx* c, const jj_table* t, size_t n, const void*
   JJ_ENTER(c);
   if (flags & ~(unsigned)(JJ_DECOMPRESS_ZIP216 | JJ_SIG_COFACTORLESS)) { c->err = "jj_sigverify_each: flags other than the ZIP-216 bit (1) and the cofactorless bit (16)"; return JJ_ERR_INVALID; }
   if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; }
   if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_sigverify_each needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
   return run_batch(c, n, {{r32, 32, 0}, {a32, 32, 1}, {s32, 32, 2}, {c32, 32, 3}}, {{verdict, 1, &c->okb}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
     const size_t ch = std::min(n, SIG_EACH_CHUNK);
@@ -773,6 +777,130 @@ JJ_API int jj_sig_challenge(jj_ctx* c, size_t n, const void* personal16, const v
   if (dr && da) hipLaunchKernelGGL(k_sig_challenge<2>, grid, block, 0, c->stream, n, (u64)personal[0], (u64)personal[1], dr, da, (const uint8_t*)dm, (u64)msg_len, (const unsigned long long*)doff, o.dev);
   else if (p0) hipLaunchKernelGGL(k_sig_challenge<1>, grid, block, 0, c->stream, n, (u64)personal[0], (u64)personal[1], p0, (const void*)nullptr, (const uint8_t*)dm, (u64)msg_len, (const unsigned long long*)doff, o.dev);
   else hipLaunchKernelGGL(k_sig_challenge<0>, grid, block, 0, c->stream, n, (u64)personal[0], (u64)personal[1], (const void*)nullptr, (const void*)nullptr, (const uint8_t*)dm, (u64)msg_len, (const unsigned long long*)doff, o.dev);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
+// ---- windowed Pedersen hashes (jj_pedersen.h: the function, the table layout, the plan; kernels k_pedersen_gather, k_pedersen_scalars, k_affine_u)
+// sum_i e[i] 16^(chunk0 + i) mod r as canonical bytes, e[i] in +-{1..4}: the positive and the negative digits as two integers, one subtraction
+static void ped_entry_scalar(const int* e, int t, int chunk0, uint8_t out[32]) {
+  u32 P[8] = {0}, N[8] = {0};
+  for (int i = 0; i < t; i++) {
+    const int bit = 4 * (chunk0 + i);
+    (e[i] > 0 ? P : N)[bit >> 5] |= (u32)(e[i] > 0 ? e[i] : -e[i]) << (bit & 31);
+  }
+  u32 d[8]; u64 br = 0, cy = 0;
+  for (int x = 0; x < 8; x++) { const u64 v = (u64)P[x] - N[x] - br; d[x] = (u32)v; br = (v >> 32) & 1u; }
+  const u32 addr = 0u - (u32)br;
+  for (int x = 0; x < 8; x++) { const u64 v = (u64)d[x] + (FR_MODULUS_W[x] & addr) + cy; d[x] = (u32)v; cy = v >> 32; }
+  memcpy(out, d, 32);
+}
+JJ_API int jj_pedersen_table_create(jj_ctx* c, int nseg, const void* gens64, int seg_chunks, int window_chunks, jj_table** out) {
+  if (!c || !out || !gens64) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (nseg < 1 || nseg > PED_MAX_SEG || seg_chunks < 1 || seg_chunks > PED_MAX_CHUNKS || window_chunks < 0 || window_chunks > PED_MAX_WINDOW) {
+    c->err = "jj_pedersen_table_create: nseg must be 1..8, seg_chunks 1..63, window_chunks 0 (default) or 1..4"; return JJ_ERR_INVALID;
+  }
+  const int w = window_chunks ? window_chunks : PED_DEFAULT_WINDOW;
+  std::vector<uint8_t> gens((size_t)nseg * 64), good((size_t)nseg);
+  if (is_device_ptr(gens64)) { HIPCHK(c, hipMemcpy(gens.data(), gens64, gens.size(), hipMemcpyDeviceToHost)); } else memcpy(gens.data(), gens64, gens.size());
+  // on the curve and torsion-free: the integer sum and the sum over scalars reduced mod r are then the same point
+  int rc;
+  if ((rc = jj_is_on_curve(c, nseg, gens.data(), good.data()))) return rc;
+  for (int j = 0; j < nseg; j++) if (!good[j]) { c->err = "jj_pedersen_table_create: a generator is not on the curve"; return JJ_ERR_INVALID; }
+  if ((rc = jj_is_torsion_free(c, nseg, gens.data(), good.data()))) return rc;
+  for (int j = 0; j < nseg; j++) if (!good[j]) { c->err = "jj_pedersen_table_create: a generator has a torsion component"; return JJ_ERR_INVALID; }
+  const size_t seg_e = ped_seg_entries(seg_chunks, w), ne = seg_e * nseg;
+  std::vector<uint8_t> s(ne * 32), p(ne * 64), aff(ne * 64);
+  size_t e = 0;
+  for (int j = 0; j < nseg; j++)
+    for (int k = 0; k < ped_windows(seg_chunks, w); k++)
+      for (int t = 1; t <= std::min(w, seg_chunks - k * w); t++)
+        for (u32 idx = 0; idx < ped_sub_entries(t); idx++, e++) {
+          int enc[PED_MAX_WINDOW];
+          for (int i = 0; i < t; i++) {
+            const u32 ch = (idx >> (3 * i)) & 7u;                     // the last chunk's sign bit is not in the index: it reads as +
+            enc[i] = (int)(1u + (ch & 1u) + (ch & 2u)) * ((ch & 4u) ? -1 : 1);
+          }
+          ped_entry_scalar(enc, t, k * w, &s[e * 32]);
+          memcpy(&p[e * 64], &gens[(size_t)j * 64], 64);
+        }
+  if ((rc = jj_varbase_mul(c, ne, s.data(), p.data(), aff.data()))) return rc;
+  auto t = std::make_unique<jj_table>();
+  t->window_bits = 0; t->device = c->device;
+  t->ped.nseg = nseg; t->ped.seg_chunks = seg_chunks; t->ped.window_chunks = w;
+  if ((rc = upload_table(c, aff.data(), ne, GNIELS_WORDS, ne * (size_t)GNIELS_WORDS * 4, &t->dev))) return rc;
+  *out = t.release();
+  return JJ_OK;
+}
+// the checks jj_pedersen_hash_vartime and jj_pedersen_scalars share: everything about the message's layout, before anything is staged
+static int ped_check_layout(jj_ctx* c, int nseg, int seg_chunks, size_t n, int prefix_bits, const void* rows, size_t row_stride, int nfields, const uint32_t* fields) {
+  if (prefix_bits < 0 || prefix_bits > 32) { c->err = "Pedersen hash: prefix_bits must be 0..32"; return JJ_ERR_INVALID; }
+  if (nfields < 0 || nfields > PED_MAX_FIELDS) { c->err = "Pedersen hash: nfields must be 0..4"; return JJ_ERR_INVALID; }
+  if (nfields && (!fields || is_device_ptr(fields))) { c->err = "Pedersen hash: fields must be a host array"; return JJ_ERR_INVALID; }
+  uint64_t bits = (uint64_t)prefix_bits;
+  for (int f = 0; f < nfields; f++) {
+    const uint64_t off = fields[2 * f], nb = fields[2 * f + 1];
+    if (nb < 1 || off + (nb + 7) / 8 > (uint64_t)row_stride) { c->err = "Pedersen hash: a field is empty or reaches past row_stride"; return JJ_ERR_INVALID; }
+    bits += nb;
+  }
+  if (bits > 3ull * (uint64_t)seg_chunks * (uint64_t)nseg) { c->err = "Pedersen hash: the message is longer than 3 * seg_chunks * nseg bits"; return JJ_ERR_INVALID; }
+  if (nfields) {
+    if (!rows) { c->err = "Pedersen hash: NULL rows"; return JJ_ERR_INVALID; }
+    if ((uint64_t)row_stride > ((uint64_t)1 << 32) || (uint64_t)n * row_stride > ((uint64_t)1 << 32)) { c->err = "Pedersen hash: more than 2^32 bytes of rows in one call"; return JJ_ERR_INVALID; }
+    if (((uintptr_t)rows & 15u) && is_device_ptr(rows)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  }
+  return JJ_OK;
+}
+JJ_API int jj_pedersen_hash_vartime(jj_ctx* c, const jj_table* t, size_t n, unsigned prefix, int prefix_bits, const void* rows, size_t row_stride, int nfields,
+                                    const uint32_t* fields, unsigned flags, void* out) {
+  if (!c || !t) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!out) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (t->ped.nseg < 1) { c->err = "jj_pedersen_hash_vartime needs a table of jj_pedersen_table_create"; return JJ_ERR_INVALID; }
+  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  if (flags & ~(unsigned)JJ_PEDERSEN_POINT) { c->err = "jj_pedersen_hash_vartime: flags other than the point bit (1)"; return JJ_ERR_INVALID; }
+  int rc;
+  if ((rc = ped_check_layout(c, t->ped.nseg, t->ped.seg_chunks, n, prefix_bits, rows, row_stride, nfields, fields))) return rc;
+  if (((uintptr_t)out & 15u) && is_device_ptr(out)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  PedSegs segs; u32 cover;
+  const std::vector<PedWin> plan = ped_build_plan(t->ped.nseg, t->ped.seg_chunks, t->ped.window_chunks, prefix, prefix_bits, nfields, fields, &segs, &cover);
+  const bool point = (flags & JJ_PEDERSEN_POINT) != 0;
+  const void *drows, *dplan;
+  OutRef o;
+  if ((rc = ensure_ext(c, n, 3)) || (!point && (rc = ensure(c, c->ws_tmp[2], 64 * n)))) return rc;
+  if ((rc = stage_in(c, 0, rows, nfields ? n * row_stride : 0, &drows)) || (rc = stage_in(c, 3, plan.data(), plan.size() * sizeof(PedWin), &dplan)) ||
+      (rc = stage_out(c, c->out[0], out, (point ? 64 : 32) * n, &o))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  prof_mark(c, 0);
+  const unsigned gblocks = (unsigned)std::min((size_t)c->cus * c->fb_gather_blocks_per_cu, (n + 255) / 256);
+  hipLaunchKernelGGL(k_pedersen_gather, dim3(gblocks), dim3(256), 0, c->stream, n, (const uint8_t*)drows, (u32)row_stride, cover, (const PedWin*)dplan, (int)plan.size(), (const u32*)t->dev, ext);
+  prof_mark(c, 1);
+  if ((rc = normalize_launch(c, n, ext, point ? o.dev : c->ws_tmp[2].p, 0))) return rc;
+  if (!point) hipLaunchKernelGGL(k_affine_u, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (const void*)c->ws_tmp[2].p, o.dev);
+  prof_mark(c, 2);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
+JJ_API int jj_pedersen_scalars(jj_ctx* c, int nseg, int seg_chunks, size_t n, unsigned prefix, int prefix_bits, const void* rows, size_t row_stride, int nfields,
+                               const uint32_t* fields, void* scalars32) {
+  if (!c) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!scalars32) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if (nseg < 1 || nseg > PED_MAX_SEG || seg_chunks < 1 || seg_chunks > PED_MAX_CHUNKS) { c->err = "jj_pedersen_scalars: nseg must be 1..8, seg_chunks 1..63"; return JJ_ERR_INVALID; }
+  int rc;
+  if ((rc = ped_check_layout(c, nseg, seg_chunks, n, prefix_bits, rows, row_stride, nfields, fields))) return rc;
+  if (((uintptr_t)scalars32 & 15u) && is_device_ptr(scalars32)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  PedSegs segs; u32 cover;
+  const std::vector<PedWin> plan = ped_build_plan(nseg, seg_chunks, PED_MAX_WINDOW, prefix, prefix_bits, nfields, fields, &segs, &cover);
+  const void *drows, *dplan;
+  OutRef o;
+  if ((rc = stage_in(c, 0, rows, nfields ? n * row_stride : 0, &drows)) || (rc = stage_in(c, 3, plan.data(), plan.size() * sizeof(PedWin), &dplan)) ||
+      (rc = stage_out(c, c->out[0], scalars32, 32 * n * (size_t)nseg, &o))) return rc;
+  hipLaunchKernelGGL(k_pedersen_scalars, dim3(blocks_for(n), (unsigned)nseg), dim3(256), 0, c->stream, n, (const uint8_t*)drows, (u32)row_stride, cover, (const PedWin*)dplan, segs, o.dev);
   bool sync = false;
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);

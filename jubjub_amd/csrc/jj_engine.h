@@ -43,6 +43,7 @@ struct jj_table {
   int device = -1;         // the table lives in this device's memory: only contexts of the same device may use it
   FbParams fp;
   FbxParams fx;            // composite table (several bases with short scalars, layout of k_fixedbase): fx.nb > 0
+  struct { int nseg, seg_chunks, window_chunks; } ped = {0, 0, 0};   // Pedersen table (jj_pedersen_table_create, layout of jj_pedersen.h): ped.nseg > 0; no other entry point takes it
   jj_table() { memset(&fx, 0, sizeof fx); }
 };
 

@@ -1166,6 +1166,75 @@ __global__ void __launch_bounds__(256) k_sig_challenge(size_t n, u64 personal_lo
   store8(c32, i, w);
 }
 #endif  // JJ_KERNELS_BATCH
+// Windowed Pedersen hashes (jj_pedersen_hash_vartime, jj_pedersen_scalars; table layout, plan and bit extraction: jj_pedersen.h).
+// k_pedersen_gather: one unit per lane and ONE accumulator for all segments -- the walk of k_fixedbase_gather (entries of GNIELS_WORDS,
+// Curve::add_signed<true>, the next window's entry fetched before the current addition), but the digit is the message's own bits: no Fr scalar,
+// no recoding addition, no launch per base.  The plan is read with wave-uniform addresses; pos < 2^32 because the entry point bounds
+// n * row_stride.  VARIABLE-TIME: the table address depends on the message.
+// k_pedersen_scalars: one (unit, segment) per lane (blockIdx.y = segment): <M_j> mod r as canonical bytes, the positive and the negative
+// chunks collected as two 252-bit integers from nibbles, then one subtraction mod r.  |<M_j>| < (r - 1) / 2, so one conditional addition of r
+// makes the difference canonical.
+}  // namespace jj
+#include "jj_pedersen.h"
+namespace jj {
+#ifdef JJ_KERNELS_BATCH
+__global__ void __launch_bounds__(256) k_pedersen_gather(size_t n, const uint8_t* __restrict__ rows, u32 row_stride, u32 cover, const PedWin* __restrict__ plan, int nwin, const u32* __restrict__ table, SoA ext) {
+  const size_t T = (size_t)gridDim.x * blockDim.x;
+  #pragma unroll 1
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += T) {
+    const u32 pos = (u32)idx * row_stride, lastd = Pedersen::last_dword(pos, cover);
+    Ext acc = Curve::identity();
+    if (nwin > 0) {
+      u32 neg;
+      u32 a = Pedersen::index(plan[0], Pedersen::raw_bits(rows, pos, lastd, plan[0]), neg);
+      ANiels e = lds_aniels(table + (size_t)a * GNIELS_WORDS);
+      #pragma unroll 1
+      for (int i = 0; i < nwin; i++) {
+        const ANiels s = e;
+        const u32 smask = neg;
+        if (i + 1 < nwin) {                                    // fetch the next window's entry before this addition
+          a = Pedersen::index(plan[i + 1], Pedersen::raw_bits(rows, pos, lastd, plan[i + 1]), neg);
+          e = lds_aniels(table + (size_t)a * GNIELS_WORDS);
+        }
+        acc = Curve::add_signed<true>(acc, s, smask);
+      }
+    }
+    ext.put(0, idx, acc.u); ext.put(1, idx, acc.v); ext.put(2, idx, acc.z);
+  }
+}
+__global__ void __launch_bounds__(256) k_pedersen_scalars(size_t n, const uint8_t* __restrict__ rows, u32 row_stride, u32 cover, const PedWin* __restrict__ plan, PedSegs segs, void* __restrict__ scalars32) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int j = (int)blockIdx.y;
+  const u32 pos = (u32)i * row_stride, lastd = Pedersen::last_dword(pos, cover);
+  u32 P[8], N[8];
+  zero8(P); zero8(N);
+  #pragma unroll 1
+  for (int k = segs.first[j]; k < segs.first[j + 1]; k++) {
+    const u32 raw = Pedersen::raw_bits(rows, pos, lastd, plan[k]);
+    #pragma unroll 1
+    for (u32 q = 0; q < plan[k].t; q++) {
+      const u32 ch = (raw >> (3u * q)) & 7u, mag = 1u + (ch & 1u) + (ch & 2u), bit = 4u * (plan[k].chunk0 + q);
+      const u32 v = mag << (bit & 31u), word = bit >> 5, sgn = 0u - (ch >> 2);
+      _Pragma("unroll") for (u32 x = 0; x < 8; x++) { const u32 m = x == word ? v : 0u; P[x] |= m & ~sgn; N[x] |= m & sgn; }
+    }
+  }
+  u32 d[8]; u64 br = 0;
+  _Pragma("unroll") for (int x = 0; x < 8; x++) { const u64 t = (u64)P[x] - N[x] - br; d[x] = (u32)t; br = (t >> 32) & 1u; }
+  const u32 addr = 0u - (u32)br;                              // P < N: add r
+  u64 cy = 0;
+  _Pragma("unroll") for (int x = 0; x < 8; x++) { const u64 t = (u64)d[x] + (FR_MODULUS_W[x] & addr) + cy; d[x] = (u32)t; cy = t >> 32; }
+  store8(scalars32, (size_t)j * n + i, d);
+}
+// the u-coordinates of affine points: the first 32 of every 64 bytes (jj_pedersen_hash_vartime without JJ_PEDERSEN_POINT)
+__global__ void __launch_bounds__(256) k_affine_u(size_t n, const void* aff64, void* out32) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 w[8];
+  load8(w, aff64, 2 * i);
+  store8(out32, i, w);
+}
+#endif  // JJ_KERNELS_BATCH
 // affine points (64 B canonical) -> table entries (AffineNiels limbs, 112 B)
 #ifdef JJ_KERNELS_BATCH
 __global__ void __launch_bounds__(256) k_affine_to_table(size_t n, const void* pts, u32* table, int stride) {

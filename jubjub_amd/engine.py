@@ -18,6 +18,7 @@ FLAG_TORSION_FREE = 2
 FLAG_NOT_SMALL_ORDER = 4
 FLAG_CLEAR_COFACTOR = 8
 FLAG_SIG_COFACTORLESS = 16     # jj_sigverify_each only
+FLAG_PEDERSEN_POINT = 1        # jj_pedersen_hash_vartime only: 64 affine bytes per unit instead of the u-coordinate
 SIG_REJECT, SIG_OK, SIG_MALFORMED = 0, 1, 2      # verdict bytes of jj_sigverify_each
 REDJUBJUB_PERSONAL = b"Zcash_RedJubjubH"         # the personalisation of RedJubjub's challenge hash: the documented example of sig_challenge's `personal` (the C library does not contain it)
 
@@ -292,6 +293,19 @@ def _msm_basis_shapes(basis_n, scalars):
     if m > basis_n:
         raise ValueError("scalars: %d terms per row, the basis has %d points" % (m, basis_n))
     return B, m, len(ss) == 2
+
+
+def _pedersen_layout(rows, fields):
+    """(n, row_stride, the C array of (byte_offset, nbits) pairs, nfields) of a pedersen call"""
+    shape = tuple(rows.shape) if hasattr(rows, "shape") else None
+    if shape is None or len(shape) != 2:
+        raise ValueError("rows: shape (n, row_stride) expected, got %r" % (shape,))
+    flat = [int(v) for f in fields for v in (f if isinstance(f, (tuple, list)) else (f,))]
+    if len(flat) % 2 or len(flat) > 8:
+        raise ValueError("fields: up to four (byte_offset, nbits) pairs expected")
+    if any(v < 0 or v >= 1 << 32 for v in flat):
+        raise ValueError("fields: values of 32 bits expected")
+    return shape[0], shape[1], (C.c_uint32 * max(len(flat), 1))(*flat), len(flat) // 2
 
 
 class _HostBlock:
@@ -727,6 +741,68 @@ class Engine:
         out, optr = self._alloc(a, n, 64)
         self._check(self._lib.jj_fixedbase_composite_mul(self._ctx, table._h, C.c_size_t(n), a.ptr, optr))
         return out
+
+    # -------------------------------------------------------------- windowed Pedersen hashes (jj_pedersen_*; the function: include/jubjub_hip.h)
+    def pedersen_table(self, gens, seg_chunks=63, window_chunks=0):
+        """The table of jj_pedersen_hash_vartime: gens (nseg, 64) affine generators, nseg 1..8, each on the curve and torsion-free;
+        seg_chunks 1..63 chunks of three bits per generator; window_chunks 1..4 chunks per table window, 0 = the default."""
+        a = _Arg(gens, 64)
+        if a.n < 1:
+            raise ValueError("gens: at least one affine point (64 bytes) expected")
+        self._bind_stream([a])
+        h = C.c_void_p()
+        self._check(self._lib.jj_pedersen_table_create(self._ctx, C.c_int(a.n), a.ptr, C.c_int(int(seg_chunks)), C.c_int(int(window_chunks)), C.byref(h)))
+        t = FixedBaseTable(self, h)
+        t.nseg, t.seg_chunks = a.n, int(seg_chunks)
+        return t
+
+    def pedersen_hash(self, table, rows, fields, prefix=0, prefix_bits=0, point=False, out=None):
+        """Windowed Pedersen hashes of n messages in one launch (jj_pedersen_hash_vartime, VARIABLE-TIME: public inputs).  Message i is
+        prefix_bits bits of `prefix` (low bits first) followed by the fields of rows[i]: rows is an (n, row_stride) uint8 array or CUDA
+        tensor, fields up to four (byte_offset, nbits) pairs, bits LSB-first within a byte.  -> (n, 32) canonical u-coordinates, or (n, 64)
+        affine points with point=True, of rows' kind, or `out`."""
+        n, stride, cf, nf = _pedersen_layout(rows, fields)
+        ra = _Arg(rows, None)
+        width = 64 if point else 32
+        if out is None:
+            out, optr = self._alloc(ra, n, width)
+        else:
+            oa = _Arg(out, width)
+            if oa.n != n or oa.torch != ra.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x %d bytes of rows' kind expected" % (n, width))
+            optr = oa.ptr
+        self._bind_stream([ra])
+        self._check(self._lib.jj_pedersen_hash_vartime(self._ctx, table._h, C.c_size_t(n), C.c_uint(int(prefix) & 0xFFFFFFFF), C.c_int(int(prefix_bits)), ra.ptr, C.c_size_t(stride),
+                                                        C.c_int(nf), cf, C.c_uint(FLAG_PEDERSEN_POINT if point else 0), optr))
+        return out
+
+    def pedersen_scalars(self, nseg, seg_chunks, rows, fields, prefix=0, prefix_bits=0):
+        """<M_j> mod r of the same messages as canonical Fr bytes, (nseg, n, 32): what fixedbase_multi_mul reads (jj_pedersen_scalars).  With
+        tables of the same generators, fixedbase_multi_mul over these scalars gives the bytes of pedersen_hash(point=True); a caller with
+        secret inputs feeds them to the constant-time LDS tables."""
+        n, stride, cf, nf = _pedersen_layout(rows, fields)
+        ra = _Arg(rows, None)
+        out, optr = self._alloc(ra, int(nseg) * n, 32)
+        self._bind_stream([ra])
+        self._check(self._lib.jj_pedersen_scalars(self._ctx, C.c_int(int(nseg)), C.c_int(int(seg_chunks)), C.c_size_t(n), C.c_uint(int(prefix) & 0xFFFFFFFF), C.c_int(int(prefix_bits)),
+                                                   ra.ptr, C.c_size_t(stride), C.c_int(nf), cf, optr))
+        return out.reshape(int(nseg), n, 32)
+
+    def pedersen_merkle(self, table, leaves, first_layer=0):
+        """The layers above n = 2^k leaves (an (n, 32) array of node u-coordinates), the root last: k calls of pedersen_hash, each over the
+        buffer of the layer below read as rows of 64 bytes -- fields (0, 255), (32, 255), the 6-bit prefix first_layer, first_layer + 1, ...
+        With a CUDA tensor nothing visits the host.  Padding a tree with empty roots is protocol and stays with the caller."""
+        shape = tuple(leaves.shape) if hasattr(leaves, "shape") else None
+        if shape is None or len(shape) != 2 or shape[1] != 32 or shape[0] < 1 or shape[0] & (shape[0] - 1):
+            raise ValueError("leaves: shape (n, 32) with n a power of two expected, got %r" % (shape,))
+        if first_layer < 0 or first_layer + shape[0].bit_length() - 1 > 64:
+            raise ValueError("layer numbers are six bits")
+        layers, cur, layer = [], leaves, int(first_layer)
+        while cur.shape[0] > 1:
+            cur = self.pedersen_hash(table, cur.reshape(cur.shape[0] // 2, 64), ((0, 255), (32, 255)), prefix=layer, prefix_bits=6)
+            layers.append(cur)
+            layer += 1
+        return layers
 
     def msm(self, scalars, points):
         return self._sum_like("jj_msm", [scalars, points], [32, 64])

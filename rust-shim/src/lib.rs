@@ -334,6 +334,33 @@ impl<'a> FixedBase<'a> {
 }
 impl Drop for FixedBase<'_> { fn drop(&mut self) { unsafe { jj_fixedbase_table_destroy(self.gpu.0, self.t); } } }
 
+/// Windowed Pedersen hashes (`jj_pedersen_*`; the function and its arguments: include/jubjub_hip.h).  VARIABLE-TIME: public inputs.
+pub struct PedersenTable<'a> { gpu: &'a Gpu, t: *mut JjTable, nseg: c_int, seg_chunks: c_int }
+impl<'a> PedersenTable<'a> {
+    /// `gens`: 1..=8 generators, each on the curve and torsion-free; `window_chunks` 0 = the default
+    pub fn new(gpu: &'a Gpu, gens: &[AffinePoint], seg_chunks: c_int, window_chunks: c_int) -> Option<Self> {
+        let (g, mut t) = (put_points(gens), std::ptr::null_mut());
+        if unsafe { jj_pedersen_table_create(gpu.0, gens.len() as c_int, g.as_ptr() as _, seg_chunks, window_chunks, &mut t) } != 0 { return None; }
+        Some(PedersenTable { gpu, t, nseg: gens.len() as c_int, seg_chunks })
+    }
+    /// One message per `row_stride` bytes of `rows`: `prefix_bits` bits of `prefix`, then the `fields` (byte_offset, nbits) -> canonical u-coordinates.
+    /// A Merkle layer over node u-coordinates: `hash(nodes, 64, &[[0, 255], [32, 255]], layer, 6)`.
+    pub fn hash(&self, rows: &[u8], row_stride: usize, fields: &[[u32; 2]], prefix: u32, prefix_bits: c_int) -> Vec<[u8; 32]> {
+        let n = if row_stride == 0 { 0 } else { rows.len() / row_stride };
+        let mut out = vec![[0u8; 32]; n];
+        assert_eq!(unsafe { jj_pedersen_hash_vartime(self.gpu.0, self.t, n, prefix, prefix_bits, rows.as_ptr() as _, row_stride, fields.len() as c_int, fields.as_ptr() as *const u32, 0, out.as_mut_ptr() as _) }, 0);
+        out
+    }
+    /// `<M_j> mod r`, segment-major (nseg x n): what `jj_fixedbase_multi_mul` reads -- the route for secret inputs, over the constant-time LDS tables
+    pub fn scalars(&self, rows: &[u8], row_stride: usize, fields: &[[u32; 2]], prefix: u32, prefix_bits: c_int) -> Vec<[u8; 32]> {
+        let n = if row_stride == 0 { 0 } else { rows.len() / row_stride };
+        let mut out = vec![[0u8; 32]; n * self.nseg as usize];
+        assert_eq!(unsafe { jj_pedersen_scalars(self.gpu.0, self.nseg, self.seg_chunks, n, prefix, prefix_bits, rows.as_ptr() as _, row_stride, fields.len() as c_int, fields.as_ptr() as *const u32, out.as_mut_ptr() as _) }, 0);
+        out
+    }
+}
+impl Drop for PedersenTable<'_> { fn drop(&mut self) { unsafe { jj_fixedbase_table_destroy(self.gpu.0, self.t); } } }
+
 /// Many scalar vectors against ONE set of points (`jj_msm_basis_*`): the points go to the device once, every call brings scalars only.
 pub struct MsmBasis<'a> { gpu: &'a Gpu, b: *mut JjMsmBasis, n: usize }
 impl<'a> MsmBasis<'a> {
