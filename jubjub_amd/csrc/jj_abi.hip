@@ -705,11 +705,10 @@ JJ_API int jj_decompress(jj_ctx* c, size_t n, const void* in32, unsigned flags, 
 constexpr size_t SIG_EACH_CHUNK = (size_t)1 << 20;      // units per chunk
 static_assert(SIG_EACH_REJECT == JJ_SIG_REJECT && SIG_EACH_OK == JJ_SIG_OK && SIG_EACH_MALFORMED == JJ_SIG_MALFORMED, "verdict bytes of jj_sig_each.h and jubjub_hip.h");
 static_assert((JJ_SIG_COFACTORLESS & (JJ_DECOMPRESS_ZIP216 | JJ_DECOMPRESS_TORSION_FREE | JJ_DECOMPRESS_NOT_SMALL_ORDER | JJ_DECOMPRESS_CLEAR_COFACTOR)) == 0, "JJ_SIG_COFACTORLESS shares a bit with a decoder flag");
-static size_t sig_each_up(size_t x) { return (x + 255) & ~(size_t)255; }
 static int sig_each_chunk(jj_ctx* c, const jj_table* t, size_t n, const void* dr, const void* da, const void* ds, const void* dc, unsigned flags, uint8_t* dverdict) {
   int rc;
   uint8_t* g = (uint8_t*)c->sigeach.p;
-  uint8_t* const pts = g; uint8_t* const ok = pts + sig_each_up(128 * n); uint8_t* const cp = ok + sig_each_up(2 * n);
+  uint8_t* const pts = g; uint8_t* const ok = pts + sig_up(128 * n); uint8_t* const cp = ok + sig_up(2 * n);
   const unsigned dflags = flags & JJ_DECOMPRESS_ZIP216;
   const int cofactored = (flags & JJ_SIG_COFACTORLESS) ? 0 : 1;
   if ((rc = decompress_dev(c, n, dr, dflags, pts, ok, false))) return rc;
@@ -731,7 +730,7 @@ JJ_API int jj_sigverify_each(jj_ctx* c, const jj_table* t, size_t n, const void*
   if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_sigverify_each needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
   return run_batch(c, n, {{r32, 32, 0}, {a32, 32, 1}, {s32, 32, 2}, {c32, 32, 3}}, {{verdict, 1, &c->okb}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
     const size_t ch = std::min(n, SIG_EACH_CHUNK);
-    int rc = ensure(c, c->sigeach, sig_each_up(128 * ch) + sig_each_up(2 * ch) + 32 * ch); if (rc) return rc;
+    int rc = ensure(c, c->sigeach, sig_up(128 * ch) + sig_up(2 * ch) + 32 * ch); if (rc) return rc;
     for (size_t lo = 0; lo < n; lo += SIG_EACH_CHUNK) {
       const size_t cn = std::min(SIG_EACH_CHUNK, n - lo);
       if ((rc = sig_each_chunk(c, t, cn, (const uint8_t*)din[0] + 32 * lo, (const uint8_t*)din[1] + 32 * lo, (const uint8_t*)din[2] + 32 * lo, (const uint8_t*)din[3] + 32 * lo, flags, (uint8_t*)dout[0] + lo))) return rc;
@@ -754,8 +753,7 @@ JJ_API int jj_sig_challenge(jj_ctx* c, size_t n, const void* personal16, const v
   uint64_t total;
   if (offsets) {
     if (is_device_ptr(offsets)) { c->err = "jj_sig_challenge: offsets must be in host memory"; return JJ_ERR_INVALID; }
-    if (offsets[0] != 0) { c->err = "jj_sig_challenge: offsets[0] must be 0"; return JJ_ERR_INVALID; }
-    for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) { c->err = "jj_sig_challenge: offsets must be non-decreasing"; return JJ_ERR_INVALID; }
+    if (!csr_offsets_ok(n, offsets)) { c->err = offsets[0] != 0 ? "jj_sig_challenge: offsets[0] must be 0" : "jj_sig_challenge: offsets must be non-decreasing"; return JJ_ERR_INVALID; }
     total = offsets[n];
   } else {
     if ((uint64_t)msg_len > SIG_CHALLENGE_MAX_BYTES) { c->err = "jj_sig_challenge: more than 2^32 message bytes in one call"; return JJ_ERR_INVALID; }

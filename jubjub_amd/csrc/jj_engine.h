@@ -292,6 +292,13 @@ struct ArgOut { void* p; size_t elem; DevBuf* buf; };
 constexpr int ARGS_IN_MAX = 4, ARGS_OUT_MAX = 2;          // = jj_ctx::in[], the outputs of jj_decompress
 static inline SoA soa_of(DevBuf& b, size_t n) { SoA s; s.base = (u32*)b.p; s.n = n; return s; }
 static inline unsigned blocks_for(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
+static inline size_t sig_up(size_t x) { return (x + 255) & ~(size_t)255; }          // the regions of the signature workspaces start on 256 bytes
+// CSR offsets of `count` runs (count + 1 entries): off[0] = 0, non-decreasing.  The callers add their own limits on count and off[count].
+static inline bool csr_offsets_ok(size_t count, const uint64_t* off) {
+  if (off[0] != 0) return false;
+  for (size_t k = 0; k < count; k++) if (off[k + 1] < off[k]) return false;
+  return true;
+}
 static const uint8_t AFFINE_IDENTITY_BYTES[64] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
 void prof_mark(jj_ctx* c, int which);
 int switch_stream(jj_ctx* c, hipStream_t s);
@@ -314,7 +321,7 @@ int stage_ensure(jj_ctx* c, size_t in_bytes, size_t out_bytes);
 int stage_in_drain(jj_ctx* c, size_t seq);
 int decompress_dev(jj_ctx* c, size_t n, const void* di, unsigned flags, void* dout, uint8_t* dok, bool prof);   // jj_abi.hip: the decoder on device pointers, on c->stream
 int jj_batch_init(jj_ctx* c);                          // jj_abi.hip: LDS carve-outs of the fixed-base kernels, square-root tables (called by jj_ctx_create)
-int msm_begin_locked(jj_ctx* c, size_t n, const void* scalars, const void* points, int part_w0, int part_stride, bool spread, jj_msm_job** out);   // jj_msm.hip
+int msm_begin_locked(jj_ctx* c, size_t n, const void* scalars, const void* points, int part_w0, int part_stride, bool spread, jj_msm_job** out, jj_msm_job* have = nullptr);   // jj_msm.hip
 void msm_job_put(jj_ctx* c, jj_msm_job* j);            // jj_msm.hip
 
 template <class Body>

@@ -306,8 +306,9 @@ void msm_job_put(jj_ctx* c, jj_msm_job* j) {
   delete j;
 }
 // spread: device-pointer jobs alternate over the context's lanes 1 .. msm_lanes (jj_msm_begin); otherwise lane 0 (jj_msm; host arrays are
-// staged through buffers the launch stream owns; JJ_MSM_LANES=1: every job)
-int msm_begin_locked(jj_ctx* c, size_t n, const void* scalars, const void* points, int part_w0, int part_stride, bool spread, jj_msm_job** out) {
+// staged through buffers the launch stream owns; JJ_MSM_LANES=1: every job).  have: a job the caller took from the pool for these n terms
+// (sig_job_open) instead of a fresh one; it is the callee's from here on, put back on failure like its own.
+int msm_begin_locked(jj_ctx* c, size_t n, const void* scalars, const void* points, int part_w0, int part_stride, bool spread, jj_msm_job** out, jj_msm_job* have) {
   size_t PASS = (size_t)1 << c->msm_pass_log2;
   // Host arrays of 2^19 terms and more are reduced in SEVERAL passes (one record each, one host tail): the copy of a pass's slice runs on the
   // copy stream beside the kernels of the pass before it -- 96 bytes per term over the link cost more than the whole reduction (2^20 terms:
@@ -318,8 +319,8 @@ int msm_begin_locked(jj_ctx* c, size_t n, const void* scalars, const void* point
   const bool split = host_in && c->msm_host_split && n >= ((size_t)1 << 19);
   PASS = msm_host_pass_terms(n, c->msm_pass_log2, split);
   const size_t npass = n ? (n + PASS - 1) / PASS : 0;
-  jj_msm_job* j;
-  int rc = msm_job_get(c, npass, &j); if (rc) return rc;
+  jj_msm_job* j = have;
+  int rc = have ? JJ_OK : msm_job_get(c, npass, &j); if (rc) return rc;
   int k = 0;
   if (spread && n && c->msm_lanes > 1 && is_device_ptr(scalars) && is_device_ptr(points)) k = 1 + (int)(c->next_lane++ % (unsigned)c->msm_lanes);
   MsmLane* L = nullptr;
@@ -369,10 +370,81 @@ JJ_API int jj_msm_begin(jj_ctx* c, size_t n, const void* scalars, const void* po
   JJ_ENTER(c);
   return msm_begin_locked(c, n, scalars, points, 0, 1, true, job);
 }
+// ---- the three batch signature entry points (jj_sigbatch_begin, _keyed_begin, _ragged) share what follows: the table of their five input arrays, the layout of
+// a workspace in 256-byte regions, the staging copy, and -- the two that return a job -- the job that owns the workspace.
+struct SigInputs {
+  struct { const void* p; size_t rows, elem; } a[5];                             // r32, a32, s32, c32, z16
+  bool dev[5];
+  size_t o_in[5];                                                                // where a staged array lies in the workspace
+  const void* in[5];                                                             // what the kernels read: the caller's device array or its staged copy
+};
+struct SigLayout {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += sig_up(bytes); return o; }
+};
+// dev[] of the table; device arrays are read with 16-byte loads
+static int sig_inputs_check(jj_ctx* c, SigInputs& t) {
+  for (int k = 0; k < 5; k++) {
+    t.dev[k] = is_device_ptr(t.a[k].p);
+    if (t.dev[k] && ((uintptr_t)t.a[k].p & 15u)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  }
+  return JJ_OK;
+}
+// regions for arrays first .. 4 where they are host arrays (the arrays before `first` have a region of the caller's: o_in[] is set)
+static void sig_inputs_place(SigInputs& t, SigLayout& lay, int first) {
+  for (int k = first; k < 5; k++) t.o_in[k] = t.dev[k] ? 0 : lay.take(t.a[k].rows * t.a[k].elem);
+}
+static int sig_to_dev(jj_ctx* c, void* dst, const void* src, size_t bytes, bool src_dev, const char* who) {
+  if (!bytes) return JJ_OK;
+  if (!src_dev && bytes >= BOUNCE_THRESHOLD && !is_pinned_host(src, bytes)) return host_to_dev_bounced(c, dst, src, bytes);
+  if (hipMemcpyAsync(dst, src, bytes, src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = std::string(who) + ": staging copy failed"; return JJ_ERR_HIP; }
+  return JJ_OK;
+}
+// in[] of the table: arrays before `first` are copied to their region wherever they lie, the others only from host memory
+static int sig_inputs_stage(jj_ctx* c, SigInputs& t, uint8_t* g, int first, const char* who) {
+  for (int k = 0; k < 5; k++) {
+    if (k >= first && t.dev[k]) { t.in[k] = t.a[k].p; continue; }
+    const int rc = sig_to_dev(c, g + t.o_in[k], t.a[k].p, t.a[k].rows * t.a[k].elem, t.dev[k], who);
+    if (rc) return rc;
+    t.in[k] = g + t.o_in[k];
+  }
+  return JJ_OK;
+}
+// The job of a batch of T terms, taken from the pool before anything is queued: its workspace *g (gdev, at least `bytes`) and its flag word in
+// the page-locked buffer are known to the kernels that write to them.  msm_begin_locked takes the job over (sig_job_submit); until then a
+// failure gives it back through sig_job_fail.
+static int sig_job_open(jj_ctx* c, size_t T, size_t bytes, jj_msm_job** job, uint8_t** g, u32** flag) {
+  const size_t PASS = msm_host_pass_terms(T, c->msm_pass_log2, false);           // device pointers: the record count msm_begin_locked computes
+  jj_msm_job* j = nullptr;
+  int rc = msm_job_get(c, (T + PASS - 1) / PASS, &j); if (rc) return rc;
+  if (j->gdev_cap < bytes) {
+    if (j->gdev) (void)hipFree(j->gdev);
+    j->gdev = nullptr; j->gdev_cap = 0;
+    if (hipMalloc(&j->gdev, bytes) != hipSuccess) { (void)hipGetLastError(); msm_job_put(c, j); c->err = "hipMalloc failed"; return JJ_ERR_NOMEM; }
+    j->gdev_cap = bytes;
+  }
+  *g = (uint8_t*)j->gdev;
+  *flag = (u32*)(j->host + j->cap - MSM_JOB_TAIL_BYTES);
+  **flag = 2u;                                                                   // neither verdict: k_sig_close has not run
+  *job = j;
+  return JJ_OK;
+}
+// synchronise first -- kernels may still be writing into the job's buffers -- then the job (if the caller still owns it) goes back to the pool
+static int sig_job_fail(jj_ctx* c, jj_msm_job* j, int code) {
+  (void)hipStreamSynchronize(c->stream); (void)hipGetLastError();
+  if (j) msm_job_put(c, j);
+  return code;
+}
+// the sum of the T prepared terms, queued on a lane like any device-pointer job, as job j's
+static int sig_job_submit(jj_ctx* c, size_t T, const void* scalars, const void* points, jj_msm_job* j, jj_msm_job** job) {
+  const int rc = msm_begin_locked(c, T, scalars, points, 0, 1, true, job, j);
+  if (rc) return sig_job_fail(c, nullptr, rc);                                   // msm_begin_locked has put the job back
+  j->sig = true;
+  return JJ_OK;
+}
 // ---- batch Schnorr verification as one MSM job (kernels: jj_sig_kernels.h).  The 2n + 1 terms are prepared on the context's stream in a
 // workspace the JOB owns (gdev: points | scalars | ok bytes | partials | B | staged host inputs), then msm_begin_locked queues the sum on a lane
 // like any device-pointer job; jj_msm_finish clears the cofactor and turns k_sig_close's flag into the (0, -1) sentinel.
-static size_t sig_up(size_t x) { return (x + 255) & ~(size_t)255; }
 JJ_API int jj_sigbatch_begin(jj_ctx* c, const void* base64, size_t n, const void* r32, const void* a32, const void* s32, const void* c32, const void* z16, unsigned flags, jj_msm_job** job) {
   if (job) *job = nullptr;
   if (!c || !job || !base64 || (flags & ~(unsigned)JJ_DECOMPRESS_ZIP216)) return JJ_ERR_INVALID;
@@ -380,69 +452,33 @@ JJ_API int jj_sigbatch_begin(jj_ctx* c, const void* base64, size_t n, const void
   if (n > (((size_t)1 << 24) - 1) / 2) return JJ_ERR_INVALID;                    // 2n + 1 terms: one pass of the MSM
   JJ_ENTER(c);
   if (n == 0) return msm_begin_locked(c, 0, nullptr, nullptr, 0, 1, true, job);   // the empty sum: [8] O = O
+  const char* const who = "jj_sigbatch_begin";
   const size_t T = 2 * n + 1;
   const u32 nblk = blocks_for(n, SIG_THREADS);
-  const struct { const void* p; size_t elem; } arr[5] = {{r32, 32}, {a32, 32}, {s32, 32}, {c32, 32}, {z16, 16}};
-  bool dev[5];
-  for (int k = 0; k < 5; k++) {
-    dev[k] = is_device_ptr(arr[k].p);
-    if (dev[k] && ((uintptr_t)arr[k].p & 15u)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
-  }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += sig_up(bytes); return o; };
-  const size_t o_pts = take(T * 64), o_scal = take(T * 32), o_ok = take(2 * n), o_part = take((size_t)nblk * SIG_PART_WORDS * 4), o_base = take(64);
-  size_t o_in[5];
-  for (int k = 0; k < 5; k++) o_in[k] = dev[k] ? 0 : take(n * arr[k].elem);
-  // The job: taken from the pool, given its workspace, and put back, so that msm_begin_locked (which takes the pool's last job) hands out this
-  // one: its page-locked buffer and its workspace are known before the kernels that write to them are queued.
-  const size_t PASS = msm_host_pass_terms(T, c->msm_pass_log2, false);
-  jj_msm_job* j0 = nullptr;
-  int rc = msm_job_get(c, (T + PASS - 1) / PASS, &j0); if (rc) return rc;
-  if (j0->gdev_cap < off) {
-    if (j0->gdev) (void)hipFree(j0->gdev);
-    j0->gdev = nullptr; j0->gdev_cap = 0;
-    if (hipMalloc(&j0->gdev, off) != hipSuccess) { (void)hipGetLastError(); msm_job_put(c, j0); c->err = "hipMalloc failed"; return JJ_ERR_NOMEM; }
-    j0->gdev_cap = off;
-  }
-  uint8_t* g = (uint8_t*)j0->gdev;
-  uint8_t* const host0 = j0->host;
-  u32* flag = (u32*)(j0->host + j0->cap - MSM_JOB_TAIL_BYTES);
-  *flag = 2u;                                                                     // neither verdict: k_sig_close has not run
-  msm_job_put(c, j0);
-  if (c->job_pool.empty() || c->job_pool.back() != j0) { c->err = "jj_sigbatch_begin: the job pool is full"; return JJ_ERR_HIP; }   // (the pool held fewer than 8 jobs: one was just taken)
-  auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };   // kernels may still be writing into the pooled job's buffers
-  const void* in[5];
-  for (int k = 0; k < 5; k++) {
-    const size_t bytes = n * arr[k].elem;
-    if (dev[k]) { in[k] = arr[k].p; continue; }
-    if (bytes >= BOUNCE_THRESHOLD && !is_pinned_host(arr[k].p, bytes)) { if ((rc = host_to_dev_bounced(c, g + o_in[k], arr[k].p, bytes))) return fail(rc); }
-    else if (hipMemcpyAsync(g + o_in[k], arr[k].p, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_begin: staging copy failed"; return fail(JJ_ERR_HIP); }
-    in[k] = g + o_in[k];
-  }
-  if (hipMemcpyAsync(g + o_base, base64, 64, is_device_ptr(base64) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_begin: staging copy failed"; return fail(JJ_ERR_HIP); }
-  if ((rc = decompress_dev(c, n, in[0], flags, g + o_pts, g + o_ok, false))) return fail(rc);
-  if ((rc = decompress_dev(c, n, in[1], flags, g + o_pts + 64 * n, g + o_ok + n, false))) return fail(rc);
-  hipLaunchKernelGGL(k_sig_terms, dim3(nblk), dim3(SIG_THREADS), 0, c->stream, n, in[2], in[3], in[4], (const uint8_t*)(g + o_ok), (void*)(g + o_pts), (void*)(g + o_scal), (u32*)(g + o_part));
+  SigInputs t = {{{r32, n, 32}, {a32, n, 32}, {s32, n, 32}, {c32, n, 32}, {z16, n, 16}}, {}, {}, {}};
+  int rc = sig_inputs_check(c, t); if (rc) return rc;
+  SigLayout lay;
+  const size_t o_pts = lay.take(T * 64), o_scal = lay.take(T * 32), o_ok = lay.take(2 * n), o_part = lay.take((size_t)nblk * SIG_PART_WORDS * 4), o_base = lay.take(64);
+  sig_inputs_place(t, lay, 0);
+  jj_msm_job* j = nullptr; uint8_t* g = nullptr; u32* flag = nullptr;
+  if ((rc = sig_job_open(c, T, lay.off, &j, &g, &flag))) return rc;
+  if ((rc = sig_inputs_stage(c, t, g, 0, who)) || (rc = sig_to_dev(c, g + o_base, base64, 64, is_device_ptr(base64), who))) return sig_job_fail(c, j, rc);
+  if ((rc = decompress_dev(c, n, t.in[0], flags, g + o_pts, g + o_ok, false))) return sig_job_fail(c, j, rc);
+  if ((rc = decompress_dev(c, n, t.in[1], flags, g + o_pts + 64 * n, g + o_ok + n, false))) return sig_job_fail(c, j, rc);
+  hipLaunchKernelGGL(k_sig_terms, dim3(nblk), dim3(SIG_THREADS), 0, c->stream, n, t.in[2], t.in[3], t.in[4], (const uint8_t*)(g + o_ok), (void*)(g + o_pts), (void*)(g + o_scal), (u32*)(g + o_part));
   hipLaunchKernelGGL(k_sig_close, dim3(1), dim3(SIG_CLOSE_THREADS), 0, c->stream, n, nblk, (const u32*)(g + o_part), (const u32*)(g + o_base), (void*)(g + o_pts), (void*)(g + o_scal), flag);
-  jj_msm_job* j = nullptr;
-  if ((rc = msm_begin_locked(c, T, g + o_scal, g + o_pts, 0, 1, true, &j))) return fail(rc);
-  if (j != j0 || j->host != host0) { (void)hipEventSynchronize(j->ev); (void)hipStreamSynchronize(c->stream); msm_job_put(c, j); c->err = "jj_sigbatch_begin: the job changed hands"; return JJ_ERR_HIP; }
-  j->sig = true;
-  *job = j;
-  return JJ_OK;
+  return sig_job_submit(c, T, g + o_scal, g + o_pts, j, job);
 }
 // ---- the same check for signatures grouped by key (kernels: jj_sig_keyed_kernels.h): n + K + 1 terms, n + K decodes in ONE decoder launch over
 // r32 | a32 copied into one region of the job's workspace (gdev: points | scalars | ok bytes | partials | B | run heads | encodings | offsets |
 // staged host inputs).  k_sig_close is launched with n = 0 on pointers moved to term n + K: it adds the partials of both kernels before it.
-// The offsets of a call, checked without a context or a device: CSR, offsets[0] = 0, non-decreasing, n + K + 1 terms in one pass of the MSM.
+// The offsets of a call, checked without a context or a device: CSR (csr_offsets_ok), n + K + 1 terms in one pass of the MSM.
 static bool sig_keyed_offsets_ok(size_t K, const uint64_t* off, size_t* n) {
   const uint64_t MAXT = (uint64_t)1 << 24;
   *n = 0;
   if (K >= MAXT) return false;
   if (!off) return K == 0;
-  if (off[0] != 0) return false;
-  for (size_t k = 0; k < K; k++) if (off[k + 1] < off[k]) return false;
-  if (off[K] > MAXT - 1 - K) return false;
+  if (!csr_offsets_ok(K, off) || off[K] > MAXT - 1 - K) return false;
   *n = (size_t)off[K];
   return true;
 }
@@ -455,65 +491,30 @@ JJ_API int jj_sigbatch_keyed_begin(jj_ctx* c, const void* base64, size_t K, cons
   if (n && (!a32 || !r32 || !s32 || !c32 || !z16)) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   if (n == 0) return msm_begin_locked(c, 0, nullptr, nullptr, 0, 1, true, job);   // the empty sum: [8] O = O
+  const char* const who = "jj_sigbatch_keyed_begin";
   const size_t T = n + K + 1;
   const u32 nblk = blocks_for(n, SIG_THREADS), kblk = blocks_for(K, SIG_THREADS);
-  const struct { const void* p; size_t rows, elem; } arr[5] = {{r32, n, 32}, {a32, K, 32}, {s32, n, 32}, {c32, n, 32}, {z16, n, 16}};
-  bool dev[5];
-  for (int k = 0; k < 5; k++) {
-    dev[k] = is_device_ptr(arr[k].p);
-    if (dev[k] && ((uintptr_t)arr[k].p & 15u)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
-  }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += sig_up(bytes); return o; };
-  const size_t o_pts = take(T * 64), o_scal = take(T * 32), o_ok = take(n + K), o_part = take((size_t)(nblk + kblk) * SIG_PART_WORDS * 4), o_base = take(64);
-  const size_t o_heads = take(n * 32), o_enc = take((n + K) * 32), o_offs = take((K + 1) * 8);
-  size_t o_in[5] = {o_enc, o_enc + 32 * n, 0, 0, 0};                               // R and A always land in the decoder's one input region
-  for (int k = 2; k < 5; k++) o_in[k] = dev[k] ? 0 : take(n * arr[k].elem);
-  // the job: taken, given its workspace and put back, as in jj_sigbatch_begin
-  const size_t PASS = msm_host_pass_terms(T, c->msm_pass_log2, false);
-  jj_msm_job* j0 = nullptr;
-  int rc = msm_job_get(c, (T + PASS - 1) / PASS, &j0); if (rc) return rc;
-  if (j0->gdev_cap < off) {
-    if (j0->gdev) (void)hipFree(j0->gdev);
-    j0->gdev = nullptr; j0->gdev_cap = 0;
-    if (hipMalloc(&j0->gdev, off) != hipSuccess) { (void)hipGetLastError(); msm_job_put(c, j0); c->err = "hipMalloc failed"; return JJ_ERR_NOMEM; }
-    j0->gdev_cap = off;
-  }
-  uint8_t* g = (uint8_t*)j0->gdev;
-  uint8_t* const host0 = j0->host;
-  u32* flag = (u32*)(j0->host + j0->cap - MSM_JOB_TAIL_BYTES);
-  *flag = 2u;                                                                     // neither verdict: k_sig_close has not run
-  msm_job_put(c, j0);
-  if (c->job_pool.empty() || c->job_pool.back() != j0) { c->err = "jj_sigbatch_keyed_begin: the job pool is full"; return JJ_ERR_HIP; }
-  auto fail = [&](int code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };   // kernels may still be writing into the pooled job's buffers
-  auto to_dev = [&](void* dst, const void* src, size_t bytes, bool src_dev) -> int {
-    if (!bytes) return JJ_OK;
-    if (!src_dev && bytes >= BOUNCE_THRESHOLD && !is_pinned_host(src, bytes)) return host_to_dev_bounced(c, dst, src, bytes);
-    if (hipMemcpyAsync(dst, src, bytes, src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_keyed_begin: staging copy failed"; return JJ_ERR_HIP; }
-    return JJ_OK;
-  };
-  const void* in[5];
-  for (int k = 0; k < 5; k++) {
-    if (k >= 2 && dev[k]) { in[k] = arr[k].p; continue; }
-    if ((rc = to_dev(g + o_in[k], arr[k].p, arr[k].rows * arr[k].elem, dev[k]))) return fail(rc);
-    in[k] = g + o_in[k];
-  }
-  if ((rc = to_dev(g + o_offs, offsets, (K + 1) * 8, false)) || (rc = to_dev(g + o_base, base64, 64, is_device_ptr(base64)))) return fail(rc);
-  if ((rc = decompress_dev(c, n + K, g + o_enc, flags, g + o_pts, g + o_ok, false))) return fail(rc);
+  SigInputs t = {{{r32, n, 32}, {a32, K, 32}, {s32, n, 32}, {c32, n, 32}, {z16, n, 16}}, {}, {}, {}};
+  int rc = sig_inputs_check(c, t); if (rc) return rc;
+  SigLayout lay;
+  const size_t o_pts = lay.take(T * 64), o_scal = lay.take(T * 32), o_ok = lay.take(n + K), o_part = lay.take((size_t)(nblk + kblk) * SIG_PART_WORDS * 4), o_base = lay.take(64);
+  const size_t o_heads = lay.take(n * 32), o_enc = lay.take((n + K) * 32), o_offs = lay.take((K + 1) * 8);
+  t.o_in[0] = o_enc; t.o_in[1] = o_enc + 32 * n;                                  // R and A always land in the decoder's one input region
+  sig_inputs_place(t, lay, 2);
+  jj_msm_job* j = nullptr; uint8_t* g = nullptr; u32* flag = nullptr;
+  if ((rc = sig_job_open(c, T, lay.off, &j, &g, &flag))) return rc;
+  if ((rc = sig_inputs_stage(c, t, g, 2, who)) || (rc = sig_to_dev(c, g + o_offs, offsets, (K + 1) * 8, false, who)) || (rc = sig_to_dev(c, g + o_base, base64, 64, is_device_ptr(base64), who)))
+    return sig_job_fail(c, j, rc);
+  if ((rc = decompress_dev(c, n + K, g + o_enc, flags, g + o_pts, g + o_ok, false))) return sig_job_fail(c, j, rc);
   const unsigned long long* doffs = (const unsigned long long*)(g + o_offs);
   u32* part = (u32*)(g + o_part);
-  hipLaunchKernelGGL(k_sig_keyed_terms, dim3(nblk), dim3(SIG_THREADS), 0, c->stream, n, (u32)K, doffs, in[2], in[3], in[4], (const uint8_t*)(g + o_ok), (void*)(g + o_pts), (void*)(g + o_scal),
+  hipLaunchKernelGGL(k_sig_keyed_terms, dim3(nblk), dim3(SIG_THREADS), 0, c->stream, n, (u32)K, doffs, t.in[2], t.in[3], t.in[4], (const uint8_t*)(g + o_ok), (void*)(g + o_pts), (void*)(g + o_scal),
                      (void*)(g + o_heads), part);
   hipLaunchKernelGGL(k_sig_keyed_close, dim3(kblk), dim3(SIG_THREADS), 0, c->stream, n, (u32)K, doffs, (const uint8_t*)(g + o_ok), (const void*)(g + o_heads), (void*)(g + o_pts), (void*)(g + o_scal),
                      part + (size_t)nblk * SIG_PART_WORDS);
   hipLaunchKernelGGL(k_sig_close, dim3(1), dim3(SIG_CLOSE_THREADS), 0, c->stream, (size_t)0, nblk + kblk, (const u32*)part, (const u32*)(g + o_base), (void*)(g + o_pts + (n + K) * 64),
                      (void*)(g + o_scal + (n + K) * 32), flag);
-  jj_msm_job* j = nullptr;
-  if ((rc = msm_begin_locked(c, T, g + o_scal, g + o_pts, 0, 1, true, &j))) return fail(rc);
-  if (j != j0 || j->host != host0) { (void)hipEventSynchronize(j->ev); (void)hipStreamSynchronize(c->stream); msm_job_put(c, j); c->err = "jj_sigbatch_keyed_begin: the job changed hands"; return JJ_ERR_HIP; }
-  j->sig = true;
-  *job = j;
-  return JJ_OK;
+  return sig_job_submit(c, T, g + o_scal, g + o_pts, j, job);
 }
 // waits for the job's records, host tail, result to out64 (host pointer: written before the call returns; device pointer: a
 // 64-byte copy queued on the context's stream).  The job is released in every case.
@@ -737,9 +738,7 @@ static void msm_ragged_plan(size_t S, const uint64_t* off, uint64_t slice_min, u
 }
 // offsets[0] = 0, non-decreasing, and S, N whose byte counts fit size_t
 static bool msm_ragged_offsets_ok(size_t S, const uint64_t* off) {
-  if (S >= SIZE_MAX / 64 || off[0] != 0) return false;
-  for (size_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return false;
-  return off[S] <= SIZE_MAX / 64;
+  return S < SIZE_MAX / 64 && csr_offsets_ok(S, off) && off[S] <= SIZE_MAX / 64;
 }
 static bool msm_ragged_plan_args(size_t S, const uint64_t* off, int& slice_min, int& waves, uint64_t& round_terms) {
   if (slice_min < 0 || waves < 0 || (S && !off) || (S && !msm_ragged_offsets_ok(S, off))) return false;
@@ -895,9 +894,7 @@ JJ_API int jj_msm_ragged(jj_ctx* c, size_t S, const uint64_t* offsets, const voi
 static bool sig_seg_offsets_ok(size_t S, const uint64_t* off, size_t* n) {
   const uint64_t MAXT = (uint64_t)1 << 24;
   *n = 0;
-  if (S > MAXT || off[0] != 0) return false;
-  for (size_t g = 0; g < S; g++) if (off[g + 1] < off[g]) return false;
-  if (off[S] > (MAXT - S) / 2) return false;                                   // 2n + S terms: one pass of the MSM for every segment, 32-bit term indices
+  if (S > MAXT || !csr_offsets_ok(S, off) || off[S] > (MAXT - S) / 2) return false;      // 2n + S terms: one pass of the MSM for every segment, 32-bit term indices
   *n = (size_t)off[S];
   return true;
 }
@@ -920,39 +917,24 @@ JJ_API int jj_sigbatch_ragged(jj_ctx* c, const void* base64, size_t S, const uin
     for (size_t g = 0; g < S; g++) memcpy((uint8_t*)out64 + 64 * g, AFFINE_IDENTITY_BYTES, 64);
     return JJ_OK;
   }
+  const char* const who = "jj_sigbatch_ragged";
   const size_t T = 2 * n + S;
-  const struct { const void* p; size_t elem; } arr[5] = {{r32, 32}, {a32, 32}, {s32, 32}, {c32, 32}, {z16, 16}};
-  bool dev[5];
-  for (int k = 0; k < 5; k++) {
-    dev[k] = is_device_ptr(arr[k].p);
-    if (dev[k] && ((uintptr_t)arr[k].p & 15u)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
-  }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += sig_up(bytes); return o; };
-  const size_t o_pts = take(T * 64), o_scal = take(T * 32), o_dec = take(2 * n * 64), o_ok = take(2 * n), o_heads = take(n * 32), o_enc = take(2 * n * 32);
-  const size_t o_offs = take((S + 1) * 8), o_bad = take(S * 4), o_base = take(64), o_b8 = take(64);
-  size_t o_in[5] = {o_enc, o_enc + 32 * n, 0, 0, 0};                           // R and A always land in the decoder's one input region
-  for (int k = 2; k < 5; k++) o_in[k] = dev[k] ? 0 : take(n * arr[k].elem);
-  int rc; OutRef o;
-  if ((rc = ensure(c, c->sigseg, off)) || (rc = stage_out(c, c->sigseg_out, out64, 64 * S, &o))) return rc;
+  SigInputs t = {{{r32, n, 32}, {a32, n, 32}, {s32, n, 32}, {c32, n, 32}, {z16, n, 16}}, {}, {}, {}};
+  int rc = sig_inputs_check(c, t); if (rc) return rc;
+  SigLayout lay;
+  const size_t o_pts = lay.take(T * 64), o_scal = lay.take(T * 32), o_dec = lay.take(2 * n * 64), o_ok = lay.take(2 * n), o_heads = lay.take(n * 32), o_enc = lay.take(2 * n * 32);
+  const size_t o_offs = lay.take((S + 1) * 8), o_bad = lay.take(S * 4), o_base = lay.take(64), o_b8 = lay.take(64);
+  t.o_in[0] = o_enc; t.o_in[1] = o_enc + 32 * n;                                // R and A always land in the decoder's one input region
+  sig_inputs_place(t, lay, 2);
+  OutRef o;
+  if ((rc = ensure(c, c->sigseg, lay.off)) || (rc = stage_out(c, c->sigseg_out, out64, 64 * S, &o))) return rc;
   uint8_t* g = (uint8_t*)c->sigseg.p;
-  auto to_dev = [&](void* dst, const void* src, size_t bytes, bool src_dev) -> int {
-    if (!src_dev && bytes >= BOUNCE_THRESHOLD && !is_pinned_host(src, bytes)) return host_to_dev_bounced(c, dst, src, bytes);
-    if (hipMemcpyAsync(dst, src, bytes, src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "jj_sigbatch_ragged: staging copy failed"; return JJ_ERR_HIP; }
-    return JJ_OK;
-  };
-  const void* in[5];
-  for (int k = 0; k < 5; k++) {
-    if (k >= 2 && dev[k]) { in[k] = arr[k].p; continue; }
-    if ((rc = to_dev(g + o_in[k], arr[k].p, n * arr[k].elem, dev[k]))) return rc;
-    in[k] = g + o_in[k];
-  }
-  if ((rc = to_dev(g + o_offs, offsets, (S + 1) * 8, false)) || (rc = to_dev(g + o_base, base64, 64, is_device_ptr(base64)))) return rc;
+  if ((rc = sig_inputs_stage(c, t, g, 2, who)) || (rc = sig_to_dev(c, g + o_offs, offsets, (S + 1) * 8, false, who)) || (rc = sig_to_dev(c, g + o_base, base64, 64, is_device_ptr(base64), who))) return rc;
   HIPCHK(c, hipMemsetAsync(g + o_bad, 0, S * 4, c->stream));
   if ((rc = jj_point_mul_by_cofactor(c, 1, g + o_base, g + o_b8))) return rc;
   if ((rc = decompress_dev(c, 2 * n, g + o_enc, flags | JJ_DECOMPRESS_CLEAR_COFACTOR, g + o_dec, g + o_ok, false))) return rc;
   const unsigned long long* doffs = (const unsigned long long*)(g + o_offs);
-  hipLaunchKernelGGL(k_sig_seg_terms, dim3(blocks_for(n, SIG_THREADS)), dim3(SIG_THREADS), 0, c->stream, n, (u32)S, doffs, in[2], in[3], in[4], (const uint8_t*)(g + o_ok), (const void*)(g + o_dec),
+  hipLaunchKernelGGL(k_sig_seg_terms, dim3(blocks_for(n, SIG_THREADS)), dim3(SIG_THREADS), 0, c->stream, n, (u32)S, doffs, t.in[2], t.in[3], t.in[4], (const uint8_t*)(g + o_ok), (const void*)(g + o_dec),
                      (void*)(g + o_pts), (void*)(g + o_scal), (void*)(g + o_heads), (u32*)(g + o_bad));
   hipLaunchKernelGGL(k_sig_seg_close, dim3(blocks_for(S, SIG_THREADS)), dim3(SIG_THREADS), 0, c->stream, (u32)S, doffs, (const void*)(g + o_heads), (const void*)(g + o_b8), (void*)(g + o_pts),
                      (void*)(g + o_scal));

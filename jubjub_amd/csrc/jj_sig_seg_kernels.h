@@ -18,17 +18,6 @@
 
 namespace jj {
 
-static JJ_DEV void sig_copy64(void* dst, size_t to, const void* src, size_t from) {
-  u32 w[8];
-  load8(w, src, 2 * from); store8(dst, 2 * to, w);
-  load8(w, src, 2 * from + 1); store8(dst, 2 * to + 1, w);
-}
-static JJ_DEV void sig_store_identity(void* points, size_t at) {
-  u32 id_u[8], id_v[8];
-  zero8(id_u); zero8(id_v); id_v[0] = 1;
-  store8(points, 2 * at, id_u); store8(points, 2 * at + 1, id_v);
-}
-
 // points / scalars: the 2n + S terms;  heads: 32 bytes per signature (see above);  bad: one word per segment
 __global__ void __launch_bounds__(SIG_THREADS) k_sig_seg_terms(size_t n, u32 S, const unsigned long long* offs, const void* s32, const void* c32, const void* z16, const uint8_t* ok,
                                                                const void* dec, void* points, void* scalars, void* heads, u32* bad) {
@@ -39,35 +28,23 @@ __global__ void __launch_bounds__(SIG_THREADS) k_sig_seg_terms(size_t n, u32 S, 
   bool head = false;
   if (i < n) {
     u32 z[8], w[8];
-    const uint4 zz = reinterpret_cast<const uint4*>(z16)[i];
-    z[0] = zz.x; z[1] = zz.y; z[2] = zz.z; z[3] = zz.w; z[4] = 0; z[5] = 0; z[6] = 0; z[7] = 0;
-    const Fe zp = Fr::unpack(z);                                       // the plain integer z < 2^128
+    const Fe zp = sig_weight(z16, i, z);
     seg = sig_key_of(offs, S, i);
     const unsigned long long lo = offs[seg];
     const size_t len = (size_t)(offs[seg + 1] - lo), at = 2 * (size_t)lo + seg + (size_t)(i - lo);      // term of R_i; A_i is len terms further
-    load8(w, c32, i);
-    const Fe t = Fr::canon_plain_product(Fr::mul(zp, Fr::from_words(w)));      // z c mod r, canonical plain (as in k_sig_terms)
+    bool c_ok, s_ok;                                                   // c is taken mod r: c_ok is not read
+    const Fe t = sig_product(zp, c32, i, c_ok);
     store8(scalars, at, z);
     Fr::pack(w, t);
     store8(scalars, at + len, w);
-    load8(w, s32, i);
-    bool s_ok;
-    const Fe sm = Fr::from_words_checked(w, s_ok);                     // s_ok: s < r
-    zs = Fr::canon_plain_product(Fr::mul(zp, sm));
+    zs = sig_product(zp, s32, i, s_ok);
     const bool r_ok = ok[i] != 0, a_ok = ok[n + i] != 0;
     if (r_ok) sig_copy64(points, at, dec, i); else sig_store_identity(points, at);
     if (a_ok) sig_copy64(points, at + len, dec, n + i); else sig_store_identity(points, at + len);
     if (!(r_ok && a_ok && s_ok)) bad[seg] = 1u;
     head = lane == 0 || lo == i;
   }
-  // segmented sum (k_sig_keyed_terms): after the step of width m a lane holds the sum of its run's lanes in [lane, lane + 2m)
-  _Pragma("unroll") for (int m = 1; m <= 32; m <<= 1) {
-    Fe o; _Pragma("unroll") for (int k = 0; k < NL; k++) o.l[k] = (u32)__shfl_down((int)zs.l[k], m, 64);
-    const u32 oseg = (u32)__shfl_down((int)seg, m, 64);
-    const Fe sum = sig_add(zs, o);
-    const u32 take = (lane + m < 64 && oseg == seg) ? 0xffffffffu : 0u;
-    zs = Fr::select(zs, sum, take);
-  }
+  sig_run_sum(zs, seg, lane);
   if (head) {
     u32 w[8];
     Fr::pack(w, zs);
@@ -75,39 +52,16 @@ __global__ void __launch_bounds__(SIG_THREADS) k_sig_seg_terms(size_t n, u32 S, 
   }
 }
 
-// One segment per lane: sigma_g = the sum of heads(g) (k_sig_keyed_close's scheme: one head is copied by its lane, a segment with more is summed by
-// its whole wave), then scalar T_g + 2 L_g = r - sigma_g mod r and point T_g + 2 L_g = [8] B.
+// One segment per lane: sigma_g = the sum of heads(g) (sig_heads_sum), then scalar T_g + 2 L_g = r - sigma_g mod r and point T_g + 2 L_g = [8] B.
 __global__ void __launch_bounds__(SIG_THREADS) k_sig_seg_close(u32 S, const unsigned long long* offs, const void* heads, const void* b8, void* points, void* scalars) {
   const u32 g = blockIdx.x * SIG_THREADS + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   unsigned long long lo = 0, hi = 0;
-  u32 cnt = 0;
-  Fe acc = Fr::zero();
-  if (g < S) {
-    lo = offs[g]; hi = offs[g + 1];
-    cnt = hi > lo ? 1u + (u32)(((hi - 1) >> 6) - (lo >> 6)) : 0u;      // heads(g)
-    if (cnt) acc = sig_load_plain(heads, (size_t)lo);
-  }
-  unsigned long long many = __ballot(cnt > 1);                         // wave-uniform
-  while (many) {
-    const int src = __ffsll((long long)many) - 1;
-    many &= many - 1;
-    const u32 first = (u32)__shfl((int)(u32)(lo >> 6), src, 64);       // n < 2^24: the wave index fits a word
-    const u32 scnt = (u32)__shfl((int)cnt, src, 64);
-    Fe v = Fr::zero();
-    for (u32 j = 1 + (u32)lane; j < scnt; j += 64) v = sig_add(v, sig_load_plain(heads, (size_t)(first + j) << 6));
-    _Pragma("unroll") for (int m = 32; m >= 1; m >>= 1) {
-      Fe o; _Pragma("unroll") for (int q = 0; q < NL; q++) o.l[q] = (u32)__shfl_xor((int)v.l[q], m, 64);
-      v = sig_add(v, o);
-    }
-    if (lane == src) acc = sig_add(acc, v);
-  }
+  if (g < S) { lo = offs[g]; hi = offs[g + 1]; }
+  const Fe acc = sig_heads_sum(lo, hi, heads, threadIdx.x & 63);
   if (g < S) {
     const size_t at = 2 * (size_t)hi + g;                              // T_g + 2 L_g
-    u32 nz = 0; _Pragma("unroll") for (int k = 0; k < NL; k++) nz |= acc.l[k];
-    Fe d; _Pragma("unroll") for (int k = 0; k < NL; k++) d.l[k] = (nz ? FrP::P[k] : 0u) - acc.l[k];
     u32 w[8];
-    Fr::pack(w, Fr::carry_full(d));
+    Fr::pack(w, sig_neg(acc));
     store8(scalars, at, w);
     sig_copy64(points, at, b8, 0);
   }
