@@ -667,6 +667,64 @@ int jj_sigverify_each(jj_ctx*, const jj_table* t, size_t n, const void* r32, con
  * that count (1962 issued, a 64-bit add being one instruction here), and the wide reduction's 486 v_mad_i64_i32 on top. */
 int jj_sig_challenge(jj_ctx*, size_t n, const void* personal16, const void* r32, const void* a32, const void* msgs, size_t msg_len, const uint64_t* offsets, void* c32);
 
+/* ---- key agreement with ONE secret scalar and its KDF, then one ChaCha20 key per row: a wallet's trial decryption on the device.
+ *   share_i  = [sk]P_i, or [8]([sk]P_i) with JJ_KA_COFACTOR, P_i = p32[i] decoded
+ *   key32[i] = BLAKE2b(personal16; to_bytes(share_i)), or BLAKE2b(personal16; to_bytes(share_i) || p32[i]) with JJ_KA_HASH_INPUT
+ * BLAKE2b as in RFC 7693 with a 32-BYTE digest (parameter word 0x01010020 -- not BLAKE2b-512 cut short), unkeyed, zero salt; the hashed string is
+ * 32 or 64 bytes: one compression.  The library still knows no protocol: the personalisation, the decoding rule and the cofactor are the
+ * caller's (the Sapling recipient: JJ_DECOMPRESS_ZIP216 | JJ_KA_COFACTOR | JJ_KA_HASH_INPUT with the personalisation "Zcash_SaplingKDF").
+ *   sk32        ONE scalar, 32 bytes, host or device: a raw pattern of which the low 252 bits are used, as in jj_varbase_mul.  It is an integer,
+ *               never reduced mod r, so the result is exact on the whole curve: points with a torsion component, sk >= r, sk = 0
+ *   p32         n x 32 encodings, decoded by the decoder of jj_decompress (k_decompress) under the JJ_DECOMPRESS_ZIP216 | _TORSION_FREE |
+ *               _NOT_SMALL_ORDER bits of flags
+ *   flags       those three bits | JJ_KA_COFACTOR | JJ_KA_HASH_INPUT; JJ_DECOMPRESS_CLEAR_COFACTOR and any other bit: JJ_ERR_INVALID
+ *   personal16  16 bytes in HOST memory, read before the call returns; NULL = sixteen zero bytes
+ *   key32 ok    n x 32 bytes and n bytes: ok[i] = 1 and the key, or, where p32[i] fails the decoder's rules, ok[i] = 0 and 32 zero bytes
+ * Pointers may be host or device, mixed freely (personal16 host only; device pointers must be 16-byte aligned).  n = 0 succeeds and touches
+ * nothing.  JJ_ERR_INVALID, before any device work and with the outputs untouched: a NULL context; flags as above; NULL sk32, p32, key32 or ok
+ * with n > 0; a misaligned device pointer.  Synchronous in the sense of jj_sigverify_each: under the context lock, on the launch stream, in
+ * chunks of 2^20 units, so the workspace is bounded by the chunk and not by n.
+ * CONSTANT-TIME in sk32 and in the share, like jj_varbase_mul: neither the instruction stream nor any memory address depends on them.  The
+ * points and the ok bytes are public, and the decoder is the variable-time one of jj_decompress.  What the claim rests on: the source discipline
+ * -- the ladder and the y-recovery are the functions of k_varbase_mont, called as they are (masked selects, no table); the one scalar is read
+ * through a per-lane address whose uniformity the compiler cannot prove (the same eight dwords in every lane), so that a wave-uniform secret
+ * does not become a scalar select or a branch on a bit of the key; the doublings, the normaliser's inversion by divsteps and the one BLAKE2b
+ * compression are straight-line code -- and the pinned instruction counts of tests/test_codegen_ka.py: the loop of the new ladder kernel has
+ * the conditional-branch count and the v_bfi_b32 count per bit of k_varbase_mont's and no memory access, no scratch, at most 168 VGPRs.  The
+ * scalar's device copy is cleared before the call returns its stream to the caller; the shares' encodings stay in the context's workspace
+ * until the next call overwrites them.
+ * Kernels, per chunk: k_decompress and its flag kernels as they are; k_varbase_mont_x1 as it is; k_varbase_mont_ka<cofactor> beside
+ * k_varbase_mont -- ONE unit per lane for every n: there is no quad-of-lanes form, as with jj_varbase_mul2_vartime, so a call of a few units
+ * pays the latency of a full ladder --; the shared normaliser writing to_bytes of the share; k_ka_kdf<hash_input>, one unit per lane.
+ * k_varbase_mont, its launch and its code are untouched.
+ * OUT OF SCOPE: per-unit scalars (the sender's side: jj_varbase_mul_compressed and a hash of the caller's), Poly1305, the note-commitment
+ * check that follows a hit, and a _vartime variant.
+ *
+ * jj_chacha20_xor: out[i][j] = in[i * in_stride + j] xor byte j of the ChaCha20 keystream (RFC 8439 section 2.3/2.4: 32-bit block counter,
+ * 96-bit nonce) of key keys32[i]; out is n x len, dense.
+ *   nonce12     12 bytes in HOST memory, read before the call returns; NULL = twelve zero bytes.  ONE nonce for all rows
+ *   counter     the block counter of a row's first 64 bytes; byte j is in block counter + j / 64, wrapping modulo 2^32
+ *   len         a multiple of 4 in 4..1024;  in_stride  a multiple of 4, >= len;  n * in_stride <= 2^32;  in and out must not overlap
+ * Any violation (and a NULL context; NULL keys32, in or out with n > 0; a misaligned device pointer) returns JJ_ERR_INVALID before any work,
+ * with out untouched.  n = 0 succeeds and touches nothing.  Pointer, lock and stream rules are those of jj_ka_kdf.  NOTHING has to happen
+ * between jj_ka_kdf with a device key32 and this call reading it as keys32: both run their kernels on the launch stream.
+ * Kernel k_chacha20_xor (jj_chacha20.h), ONE launch, one row per lane: the 16 state words and the 16 working words in registers, the 20 rounds
+ * unrolled, each rotation one v_alignbit_b32, no scratch; rows are read and written as aligned dwords (what the multiple-of-4 rule buys at
+ * every skew), and nothing is read past a row's len bytes.  The compact-note shape is len = in_stride = 52, counter = 1: one block; the 564
+ * bytes of a full note ciphertext are nine.
+ * Measured on an MI355X (profiles/ka_kdf_ab.txt: device-resident inputs and results, three alternating rounds of one process per route, median; the
+ * old route on a build of the parent commit): 2^20 units of the Sapling recipient's shape 14.28 ms per jj_ka_kdf call (73.4 M keys/s), 14.43 ms with
+ * the cipher at len 52 behind it, against 14.39 ms for the four-call composed route (jj_decompress, jj_varbase_mul with the scalar written n times,
+ * jj_point_mul_by_cofactor, jj_compress), which has NO hash, 165 ms with the shares hashed by hashlib in 16 processes and 529 ms in one thread; 2^16:
+ * 1.688 against 1.705 ms (6.9 ms with 16 hashing processes).  Traced kernels of one 2^20 call: k_decompress<8> 2.3 ms, k_varbase_mont_x1 0.17,
+ * k_varbase_mont_ka<true> 12.3 - 14.2 over four traced calls, k_normalize<16> 0.11, k_ka_kdf<true> 0.06, k_chacha20_xor 0.13.  BEHIND at small n: 2^10 units take 1.244 ms against 0.744 ms for the
+ * composed route, whose ladder runs one scalar multiplication per quad of lanes up to vb_quad_max units at a third of the latency; this call has no
+ * such form.  With the hash a caller needs the old route is 1.21 ms there: level. */
+#define JJ_KA_COFACTOR   32u   /* share = [8]([sk]P) instead of [sk]P */
+#define JJ_KA_HASH_INPUT 64u   /* hash share32 || p32[i] instead of share32 alone */
+int jj_ka_kdf(jj_ctx*, size_t n, const void* sk32, const void* p32, unsigned flags, const void* personal16, void* key32, uint8_t* ok);
+int jj_chacha20_xor(jj_ctx*, size_t n, const void* keys32, const void* nonce12, unsigned counter, const void* in, size_t len, size_t in_stride, void* out);
+
 /* ---- windowed Pedersen hashes: one launch for n units, every segment in one accumulator.  VARIABLE-TIME (public inputs): the table address
  * depends on the message; a caller with secret inputs composes jj_pedersen_scalars with jj_fixedbase_multi_mul on the LDS tables.
  * A message M is `prefix_bits` bits of `prefix` (low bits first), then up to four fields of the unit's row; every bit is taken LSB-first within

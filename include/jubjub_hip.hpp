@@ -529,6 +529,26 @@ inline std::vector<Bytes32> sig_challenge(const Context& c, const std::vector<By
   c.check(jj_sig_challenge(c.raw(), n, personal ? personal->data() : nullptr, R.empty() ? nullptr : R.data(), A.empty() ? nullptr : A.data(), flat.data(), 0, offsets.data(), out.data()));
   return out;
 }
+// Key agreement with ONE secret scalar and its KDF (jj_ka_kdf): keys[i] = BLAKE2b-256(personal; to_bytes(share_i) [|| P[i]]), share_i = [sk]P_i or
+// [8]([sk]P_i); flags: the decoder's JJ_DECOMPRESS_ZIP216 | _TORSION_FREE | _NOT_SMALL_ORDER bits | JJ_KA_COFACTOR | JJ_KA_HASH_INPUT.  ok[i] = 0
+// and a zero key where P[i] does not decode.  CONSTANT-TIME in sk and in the shares.  personal == nullptr is sixteen zero bytes (the Sapling
+// recipient: "Zcash_SaplingKDF" with JJ_DECOMPRESS_ZIP216 | JJ_KA_COFACTOR | JJ_KA_HASH_INPUT).
+struct KaKeys { std::vector<Bytes32> keys; std::vector<uint8_t> ok; };
+inline KaKeys ka_kdf(const Context& c, const Bytes32& sk, const std::vector<Bytes32>& P, unsigned flags, const std::array<uint8_t, 16>* personal = nullptr) {
+  KaKeys r{std::vector<Bytes32>(P.size()), std::vector<uint8_t>(P.size())};
+  c.check(jj_ka_kdf(c.raw(), P.size(), sk.data(), P.data(), flags, personal ? personal->data() : nullptr, r.keys.data(), r.ok.data()));
+  return r;
+}
+// One RFC 8439 ChaCha20 key per row (jj_chacha20_xor): rows of `len` bytes at a stride of in_stride in `in`, a dense n x len result; len and
+// in_stride multiples of 4, len in 4..1024; nonce == nullptr is twelve zero bytes.
+inline std::vector<uint8_t> chacha20_xor(const Context& c, const std::vector<Bytes32>& keys, const std::vector<uint8_t>& in, size_t len, size_t in_stride, uint32_t counter = 0,
+                                         const std::array<uint8_t, 12>* nonce = nullptr) {
+  const size_t n = keys.size();
+  if (n && in.size() < (n - 1) * in_stride + len) throw Error(JJ_ERR_INVALID, "length mismatch");
+  std::vector<uint8_t> out(n * len);
+  c.check(jj_chacha20_xor(c.raw(), n, keys.data(), nonce ? nonce->data() : nullptr, counter, in.data(), len, in_stride, out.data()));
+  return out;
+}
 // MSM cut into parts (jj_msm_partial / jj_msm_combine): part g of G by windows (every part sees all terms) or all windows of a slice
 // of the terms; the records are combined in one host tail
 using MsmRecord = std::array<uint8_t, JJ_MSM_PARTIAL_BYTES>;

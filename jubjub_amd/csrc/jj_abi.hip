@@ -779,6 +779,82 @@ JJ_API int jj_sig_challenge(jj_ctx* c, size_t n, const void* personal16, const v
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
 }
+// ---- key agreement and KDF with ONE secret scalar (a wallet's trial decryption): key32[i] = BLAKE2b-256(personal16; to_bytes(share_i) [|| p32[i]]),
+// share_i = [sk]P_i or [8]([sk]P_i), P_i = the decoder's reading of p32[i].  CONSTANT-TIME in sk and in the shares; the points and ok bytes are
+// public.  Every argument is checked before anything is staged or launched.  Per chunk of KA_CHUNK units, queued one after another on the launch
+// stream: decompress_dev as it is (a refused encoding leaves (0, 0) and ok = 0: the ladder then runs on x1 = 1, an ordinary value, and the unit's
+// key is zeroed at the end), k_varbase_mont_x1 as it is, k_varbase_mont_ka (the ladder of k_varbase_mont with the one scalar read for all lanes
+// and the three doublings of the cofactor as a template flag; one unit per lane for every n), the shared normaliser in mode 1 (to_bytes of the
+// share: 32 bytes per unit, not 64), k_ka_kdf.  The workspace (c->ka: the scalar's device copy, 64 + 32 bytes per unit of a chunk; the
+// decoder's, the ladder's and the normaliser's own) is bounded by the chunk; host arrays are staged whole by the front end like every entry
+// point's.  The scalar's device copy is cleared behind the last chunk.
+constexpr size_t KA_CHUNK = (size_t)1 << 20;            // units per chunk
+constexpr unsigned KA_DECODER_FLAGS = JJ_DECOMPRESS_ZIP216 | JJ_DECOMPRESS_TORSION_FREE | JJ_DECOMPRESS_NOT_SMALL_ORDER;
+static_assert(((JJ_KA_COFACTOR | JJ_KA_HASH_INPUT) & (KA_DECODER_FLAGS | JJ_DECOMPRESS_CLEAR_COFACTOR | JJ_SIG_COFACTORLESS)) == 0 && (JJ_KA_COFACTOR & JJ_KA_HASH_INPUT) == 0,
+              "the JJ_KA_* flags share a bit with another flag");
+static int ka_chunk(jj_ctx* c, size_t n, const void* dp, unsigned flags, const uint64_t (&personal)[2], void* dkey, uint8_t* dok) {
+  int rc;
+  uint8_t* const sk = (uint8_t*)c->ka.p; uint8_t* const pts = sk + 256; uint8_t* const enc = pts + sig_up(64 * n);
+  if ((rc = decompress_dev(c, n, dp, flags & KA_DECODER_FLAGS, pts, dok, false))) return rc;
+  if ((rc = ensure_ext(c, n, 3))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  hipLaunchKernelGGL(k_varbase_mont_x1, dim3(blocks_for(64 * ((n + 64 * MONT_X1_UNITS - 1) / (64 * MONT_X1_UNITS)))), dim3(256), 0, c->stream, n, (const void*)pts, ext);
+  if (flags & JJ_KA_COFACTOR) hipLaunchKernelGGL(k_varbase_mont_ka<true>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (const u32*)sk, (const void*)pts, ext);
+  else hipLaunchKernelGGL(k_varbase_mont_ka<false>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (const u32*)sk, (const void*)pts, ext);
+  if ((rc = normalize_launch(c, n, ext, enc, 1))) return rc;
+  if (flags & JJ_KA_HASH_INPUT) hipLaunchKernelGGL(k_ka_kdf<true>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)personal[0], (u64)personal[1], (const void*)enc, dp, (const uint8_t*)dok, dkey);
+  else hipLaunchKernelGGL(k_ka_kdf<false>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)personal[0], (u64)personal[1], (const void*)enc, dp, (const uint8_t*)dok, dkey);
+  return JJ_OK;
+}
+JJ_API int jj_ka_kdf(jj_ctx* c, size_t n, const void* sk32, const void* p32, unsigned flags, const void* personal16, void* key32, uint8_t* ok) {
+  if (!c) return JJ_ERR_INVALID;
+  if (flags & ~(KA_DECODER_FLAGS | JJ_KA_COFACTOR | JJ_KA_HASH_INPUT)) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!sk32 || !p32 || !key32 || !ok) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  for (const void* p : {sk32, p32, (const void*)key32, (const void*)ok})
+    if (((uintptr_t)p & 15u) && is_device_ptr(p)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  uint64_t personal[2] = {0, 0};
+  if (personal16) memcpy(personal, personal16, 16);
+  return run_batch(c, n, {{p32, 32, 0}}, {{key32, 32, &c->out[0]}, {ok, 1, &c->okb}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    const size_t ch = std::min(n, KA_CHUNK);
+    int rc = ensure(c, c->ka, 256 + sig_up(64 * ch) + 32 * ch); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->ka.p, sk32, 32, is_device_ptr(sk32) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    for (size_t lo = 0; lo < n; lo += KA_CHUNK) {
+      const size_t cn = std::min(KA_CHUNK, n - lo);
+      if ((rc = ka_chunk(c, cn, (const uint8_t*)din[0] + 32 * lo, flags, personal, (uint8_t*)dout[0] + 32 * lo, (uint8_t*)dout[1] + lo))) return rc;
+    }
+    HIPCHK(c, hipMemsetAsync(c->ka.p, 0, 32, c->stream));
+    return JJ_OK;
+  });
+}
+// ---- one RFC 8439 ChaCha20 key per row (kernel: k_chacha20_xor in jj_kernels.h; jj_chacha20.h): out[i][j] = in[i * in_stride + j] xor byte j of
+// the keystream of keys32[i] under nonce12, block counter from `counter`.  Every argument is checked before anything is staged or launched; ONE
+// launch over all n rows, no workspace.  A host `in` is staged as the (n - 1) * in_stride + len bytes that are read.  keys32 is read on the
+// launch stream, where jj_ka_kdf wrote it: nothing has to happen between the two calls.
+JJ_API int jj_chacha20_xor(jj_ctx* c, size_t n, const void* keys32, const void* nonce12, unsigned counter, const void* in, size_t len, size_t in_stride, void* out) {
+  if (!c) return JJ_ERR_INVALID;
+  if (len < 4 || len > 1024 || (len & 3u) || (in_stride & 3u) || in_stride < len) return JJ_ERR_INVALID;
+  if (n > ((uint64_t)1 << 32) / in_stride) return JJ_ERR_INVALID;                    // n * in_stride <= 2^32
+  if (n == 0) return JJ_OK;
+  if (!keys32 || !in || !out) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  const size_t in_bytes = (n - 1) * in_stride + len, out_bytes = n * len;
+  if ((uintptr_t)in < (uintptr_t)out + out_bytes && (uintptr_t)out < (uintptr_t)in + in_bytes) { c->err = "jj_chacha20_xor: in and out overlap"; return JJ_ERR_INVALID; }
+  for (const void* p : {keys32, in, (const void*)out})
+    if (((uintptr_t)p & 15u) && is_device_ptr(p)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  uint32_t nonce[3] = {0, 0, 0};
+  if (nonce12) memcpy(nonce, nonce12, 12);
+  int rc;
+  const void *dk, *di;
+  OutRef o;
+  if ((rc = stage_in(c, 0, keys32, 32 * n, &dk)) || (rc = stage_in(c, 1, in, in_bytes, &di)) || (rc = stage_out(c, c->out[0], out, out_bytes, &o))) return rc;
+  hipLaunchKernelGGL(k_chacha20_xor, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dk, (u32)nonce[0], (u32)nonce[1], (u32)nonce[2], (u32)counter, (const uint8_t*)di, (u32)(len / 4), in_stride,
+                     (uint8_t*)o.dev);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
 // ---- windowed Pedersen hashes (jj_pedersen.h: the function, the table layout, the plan; kernels k_pedersen_gather, k_pedersen_scalars, k_affine_u)
 // sum_i e[i] 16^(chunk0 + i) mod r as canonical bytes, e[i] in +-{1..4}: the positive and the negative digits as two integers, one subtraction
 static void ped_entry_scalar(const int* e, int t, int chunk0, uint8_t out[32]) {

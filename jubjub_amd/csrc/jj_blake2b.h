@@ -1,8 +1,12 @@
-// BLAKE2b-512 (RFC 7693), one message per lane: the compression function and a streaming "absorb up to three parts, finish" routine -- device
+// BLAKE2b (RFC 7693; BLAKE2b-512 unless told otherwise), one message per lane: the compression function and a streaming "absorb up to three parts, finish" routine -- device
 // code, everything in registers.  Unkeyed, 64-byte digest, zero salt, a 16-byte personalisation: parameter block word 0 = 0x01010040 xored into
 // h[0], the personalisation into h[6] and h[7]; t counts bytes in its low 64-bit word only (t1 = 0: inputs stay far below 2^64 bytes); f0 is set
 // on the last block, and the last block of an empty input is one zero block with t = 0.
-// Included by jj_kernels.h (k_sig_challenge, jj_sig_challenge) and, with -DJJ_HOST_EMU, by tests/cpp/emu_blake2b.cpp.
+// Included by jj_kernels.h (k_sig_challenge, jj_sig_challenge; k_ka_kdf, jj_ka_kdf) and, with -DJJ_HOST_EMU, by tests/cpp/emu_blake2b.cpp and
+// tests/cpp/emu_ka.cpp.
+// The digest length is a compile-time parameter (Blake2bT<DIGEST>, 1..64 bytes; Blake2b = Blake2bT<64>): it enters the parameter word only --
+// BLAKE2b-256 is another hash than BLAKE2b-512 cut short -- and the first DIGEST bytes of h are the digest.  hash_parts is the one-compression
+// form jj_ka_kdf uses: one or two 32-byte parts and nothing else.
 //
 // Number format: uint64_t for the state, the message words, the additions and the xors; hipcc lowers a 64-bit add to v_add_co_u32 +
 // v_addc_co_u32 and an xor to two v_xor_b32, which is what code on explicit register pairs would be.  The rotations are NOT left to the 64-bit
@@ -24,7 +28,9 @@
 
 namespace jj {
 
-struct Blake2b {
+template <int DIGEST = 64>
+struct Blake2bT {
+  static_assert(DIGEST >= 1 && DIGEST <= 64, "BLAKE2b digest length");
   static constexpr u64 IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
                                 0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
   static constexpr uint8_t SIGMA[10][16] = {
@@ -33,7 +39,7 @@ struct Blake2b {
       {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
       {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
       {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0}};
-  static constexpr u32 PARAM0 = 0x01010040u;      // digest length 64, key length 0, fanout 1, depth 1
+  static constexpr u32 PARAM0 = 0x01010000u | (u32)DIGEST;      // digest length (0x01010040 for 64, 0x01010020 for 32), key length 0, fanout 1, depth 1
 
   // (hi : lo) >> sh for sh in [0, 32): v_alignbit_b32
   static JJ_DEV u32 funnel(u32 hi, u32 lo, u32 sh) {
@@ -82,7 +88,7 @@ struct Blake2b {
     round<6>(v, m); round<7>(v, m); round<8>(v, m); round<9>(v, m); round<10>(v, m); round<11>(v, m);
     _Pragma("unroll") for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
   }
-  // h of an unkeyed 64-byte digest with the 16 bytes of personalisation given as two little-endian words
+  // h of an unkeyed DIGEST-byte digest with the 16 bytes of personalisation given as two little-endian words
   static JJ_DEV void init(u64 (&h)[8], u64 personal_lo, u64 personal_hi) {
     _Pragma("unroll") for (int i = 0; i < 8; i++) h[i] = IV[i];
     h[0] ^= PARAM0; h[6] ^= personal_lo; h[7] ^= personal_hi;
@@ -141,6 +147,21 @@ struct Blake2b {
     }
     _Pragma("unroll") for (int i = 0; i < 4; i++) { lo[2 * i] = (u32)h[i]; lo[2 * i + 1] = (u32)(h[i] >> 32); hi[2 * i] = (u32)h[4 + i]; hi[2 * i + 1] = (u32)(h[4 + i] >> 32); }
   }
+
+  // out <- the first 32 bytes of h after ONE compression over part0 (PARTS = 1: 32 bytes hashed) or part0 || part1 (PARTS = 2: 64 bytes): the
+  // whole digest when DIGEST = 32.  Straight-line code: no load, no branch, nothing indexed at run time.
+  template <int PARTS>
+  static JJ_DEV void hash_parts(u32 (&out)[8], u64 personal_lo, u64 personal_hi, const u32 (&part0)[8], const u32 (&part1)[8]) {
+    static_assert(PARTS == 1 || PARTS == 2, "one or two 32-byte parts");
+    u64 h[8], m[16];
+    init(h, personal_lo, personal_hi);
+    words32(m, 0, part0);
+    if constexpr (PARTS == 2) words32(m, 4, part1);
+    _Pragma("unroll") for (int k = 4 * PARTS; k < 16; k++) m[k] = 0;
+    compress(h, m, 32u * PARTS, true);
+    _Pragma("unroll") for (int i = 0; i < 4; i++) { out[2 * i] = (u32)h[i]; out[2 * i + 1] = (u32)(h[i] >> 32); }
+  }
 };
+typedef Blake2bT<64> Blake2b;
 
 }  // namespace jj

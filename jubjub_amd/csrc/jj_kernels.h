@@ -706,6 +706,37 @@ __global__ void __launch_bounds__(256, 3) k_varbase_mont(size_t n, const void* s
   varbase_mont_recover(P, ext.get(2, i), last, xq, zq, xp, zp, u, v, z);
   ext.put(0, i, u); ext.put(1, i, v); ext.put(2, i, z);
 }
+// The same ladder with ONE scalar for every unit (jj_ka_kdf: a key agreement's secret against n public points), one unit per lane for every n
+// -- there is no quad-of-lanes form --, and with COFACTOR three Edwards doublings behind the recovery: [8]([k]P) as projective (U : V : Z).
+// CONSTANT-TIME in the scalar and in the result like k_varbase_mont: varbase_mont_ladder and varbase_mont_recover are called as they are.
+// A wave-uniform secret invites the compiler to keep the Gray-code bits in scalar registers and to turn the masked select of a step into a
+// scalar select or a branch on a bit of the key.  The eight dwords are therefore read through a per-lane address -- scalar8 plus an offset
+// that is zero in every lane but comes out of an empty asm statement with a vector-register constraint, which the compiler can prove neither
+// zero nor uniform --, so the key lives in vector registers as in k_varbase_mont and the loop is the same loop (tests/test_codegen_ka.py: the
+// same branch and v_bfi_b32 counts per bit, no memory access, no scratch, at most 168 VGPRs).
+// Bounds of the doublings: the recovered (U, V, Z) are products or the masked-in constants and loaded coordinates, inside the accumulator
+// class of tools/bounds_check.py check_curve (check_ka_cofactor holds that), whose fixed point iterates dbl over every member: dbl-after-
+// recovery is dbl(inv) there, dbl-after-dbl is its own member.
+template <bool COFACTOR>
+__global__ void __launch_bounds__(256, 3) k_varbase_mont_ka(size_t n, const u32* scalar8, const void* points, SoA ext) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 lane_zero = 0;
+  asm volatile("" : "+v"(lane_zero));                       // zero in every lane; divergent as far as the compiler knows
+  const u32* kp = scalar8 + lane_zero;
+  u32 k[8];
+  _Pragma("unroll") for (int q = 0; q < 8; q++) k[q] = kp[q];
+  Fe u, v, z, xq, zq, xp, zp;
+  const u32 last = varbase_mont_ladder(ext.get(2, i), k, xq, zq, xp, zp);
+  const Affine P = load_affine(points, i);
+  varbase_mont_recover(P, ext.get(2, i), last, xq, zq, xp, zp, u, v, z);
+  if constexpr (COFACTOR) {
+    Ext e; e.u = u; e.v = v; e.z = z; e.t1 = u; e.t2 = v;   // (Curve::dbl reads u, v, z only)
+    e = Curve::dbl(Curve::dbl(Curve::dbl(e)));
+    u = e.u; v = e.v; z = e.z;
+  }
+  ext.put(0, i, u); ext.put(1, i, v); ext.put(2, i, z);
+}
 #endif  // JJ_KERNELS_BATCH
 
 // ------------------------------------------------------------------------------------------------ K4: fixed-base
@@ -1164,6 +1195,42 @@ __global__ void __launch_bounds__(256) k_sig_challenge(size_t n, u64 personal_lo
   u32 w[8];
   Fr::to_words(w, Fr::from_words_wide(lo, hi));
   store8(c32, i, w);
+}
+#endif  // JJ_KERNELS_BATCH
+// The hash of a key agreement (jj_ka_kdf): key32[i] = BLAKE2b-256(personal; share_i) or, with INPUT, BLAKE2b-256(personal; share_i || p32[i]),
+// one unit per lane, ONE compression with the parameter word 0x01010020 (Blake2bT<32>::hash_parts).  share32 holds to_bytes of the shares as the
+// shared normaliser wrote them (mode 1: the canonical v with the sign of u in bit 255), so the encoding is formed before it gets here and this
+// kernel only loads it.  A unit whose ok byte is 0 (the decoder refused p32[i]; public) stores 32 zero bytes.  Straight-line code in the
+// share: no branch, no address and no select depends on it.
+#ifdef JJ_KERNELS_BATCH
+template <bool INPUT>
+__global__ void __launch_bounds__(256) k_ka_kdf(size_t n, u64 personal_lo, u64 personal_hi, const void* share32, const void* p32, const uint8_t* ok, void* key32) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 a[8], b[8], w[8];
+  load8(a, share32, i);
+  if constexpr (INPUT) load8(b, p32, i); else zero8(b);
+  Blake2bT<32>::hash_parts<INPUT ? 2 : 1>(w, personal_lo, personal_hi, a, b);
+  if (!ok[i]) zero8(w);
+  store8(key32, i, w);
+}
+#endif  // JJ_KERNELS_BATCH
+// One RFC 8439 ChaCha20 key per row (jj_chacha20_xor, jj_chacha20.h): out[i][0 .. len) = in[i * in_stride .. + len) xor the keystream of
+// keys32[i] from block `counter` on, one row per lane.  len = 4 * nwords and in_stride are multiples of 4 and both bases 4-byte aligned (the
+// entry point asks 16 of a device pointer), so every access is an aligned dword; the byte offset of a row is formed in 64 bits (n * in_stride
+// may reach 2^32).  Nothing is read past a row's len bytes, nothing written outside the dense n x len output.
+}  // namespace jj
+#include "jj_chacha20.h"
+namespace jj {
+#ifdef JJ_KERNELS_BATCH
+__global__ void __launch_bounds__(256) k_chacha20_xor(size_t n, const void* keys32, u32 nonce0, u32 nonce1, u32 nonce2, u32 counter, const uint8_t* in, u32 nwords,
+                                                      size_t in_stride, uint8_t* out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 key[8];
+  load8(key, keys32, i);
+  const u32 nonce[3] = {nonce0, nonce1, nonce2};
+  ChaCha20::xor_row(reinterpret_cast<const u32*>(in + i * in_stride), reinterpret_cast<u32*>(out + i * (size_t)nwords * 4), nwords, key, counter, nonce);
 }
 #endif  // JJ_KERNELS_BATCH
 // Windowed Pedersen hashes (jj_pedersen_hash_vartime, jj_pedersen_scalars; table layout, plan and bit extraction: jj_pedersen.h).

@@ -21,6 +21,10 @@ FLAG_SIG_COFACTORLESS = 16     # jj_sigverify_each only
 FLAG_PEDERSEN_POINT = 1        # jj_pedersen_hash_vartime only: 64 affine bytes per unit instead of the u-coordinate
 SIG_REJECT, SIG_OK, SIG_MALFORMED = 0, 1, 2      # verdict bytes of jj_sigverify_each
 REDJUBJUB_PERSONAL = b"Zcash_RedJubjubH"         # the personalisation of RedJubjub's challenge hash: the documented example of sig_challenge's `personal` (the C library does not contain it)
+SAPLING_KDF_PERSONAL = b"Zcash_SaplingKDF"       # the personalisation of the Sapling KDF: the documented example of ka_kdf's `personal` (the C library does not contain it)
+FLAG_KA_COFACTOR = 32          # jj_ka_kdf only: share = [8]([sk]P)
+FLAG_KA_HASH_INPUT = 64        # jj_ka_kdf only: hash share || encoding
+KA_SAPLING_FLAGS = FLAG_ZIP216 | FLAG_KA_COFACTOR | FLAG_KA_HASH_INPUT      # the Sapling recipient's ka_kdf flags
 
 
 class JubjubError(RuntimeError):
@@ -306,6 +310,16 @@ def _pedersen_layout(rows, fields):
     if any(v < 0 or v >= 1 << 32 for v in flat):
         raise ValueError("fields: values of 32 bits expected")
     return shape[0], shape[1], (C.c_uint32 * max(len(flat), 1))(*flat), len(flat) // 2
+
+
+def _fixed_bytes(x, size, name):
+    """a short host-side argument (personalisation, nonce) as bytes of exactly `size`, or None"""
+    if x is None:
+        return None
+    x = bytes(x)
+    if len(x) != size:
+        raise ValueError("%s: %d bytes expected, got %d" % (name, size, len(x)))
+    return x
 
 
 class _HostBlock:
@@ -1102,6 +1116,71 @@ class Engine:
         """sig_challenge(R, A, msgs, personal, offsets), then sigbatch_verify with those challenges -> "ok" | "reject" | "malformed".  With R on
         the device the challenges never visit the host."""
         return self.sigbatch_verify(base, R, A, s, self.sig_challenge(R, A, msgs, personal, offsets), z, zip216)
+
+    def ka_kdf(self, sk, P, personal=None, flags=KA_SAPLING_FLAGS, out=None):
+        """Key agreement with ONE secret scalar and its KDF (jj_ka_kdf) -> (keys (n, 32), ok (n,)):
+        keys[i] = BLAKE2b-256(personal; to_bytes(share_i) [|| P[i] with FLAG_KA_HASH_INPUT]), share_i = [sk]P_i, or [8]([sk]P_i) with
+        FLAG_KA_COFACTOR, P_i decoded under the FLAG_ZIP216 | FLAG_TORSION_FREE | FLAG_NOT_SMALL_ORDER bits of `flags` (the default is the
+        Sapling recipient's set; SAPLING_KDF_PERSONAL its personalisation).  sk: 32 bytes (bytes, a uint8 array or a CUDA tensor), an integer
+        of which the low 252 bits are used, never reduced mod r.  P: (n, 32) encodings, a numpy array or a torch CUDA tensor; the results are
+        of P's kind, or `out` = (keys, ok).  Where P[i] fails the decoder, ok[i] = 0 and keys[i] is zero.  CONSTANT-TIME in sk and in the
+        shares; the points are public.  A device result may be handed straight to chacha20_xor: it reads the keys on the same stream."""
+        personal = _fixed_bytes(personal, 16, "personal")
+        if not hasattr(P, "shape") or len(P.shape) != 2 or P.shape[1] != 32:
+            raise ValueError("P: shape (n, 32) expected, got %r" % (tuple(P.shape) if hasattr(P, "shape") else None,))
+        n = P.shape[0]
+        ska, pa = _Arg(sk, 32), _Arg(P, 32)
+        if ska.n != 1:
+            raise ValueError("sk: ONE scalar of 32 bytes expected, got %d" % ska.n)
+        if out is None:
+            (keys, kptr), (ok, okptr) = self._alloc(pa, n, 32), self._alloc(pa, n, 1)
+        else:
+            keys, ok = out
+            ka, oa = _Arg(keys, 32), _Arg(ok, 1)
+            if ka.n != n or oa.n != n or ka.torch != pa.torch or oa.torch != pa.torch or ka.keep is not keys or oa.keep is not ok:
+                raise ValueError("out: (keys, ok), contiguous uint8 arrays of %d x 32 and %d bytes of P's kind expected" % (n, n))
+            kptr, okptr = ka.ptr, oa.ptr
+        self._bind_stream([pa, ska])
+        self._check(self._lib.jj_ka_kdf(self._ctx, C.c_size_t(n), ska.ptr, pa.ptr, C.c_uint(flags), personal, kptr, okptr))
+        return keys, ok
+
+    def chacha20_xor(self, keys, data, nonce=None, counter=0, length=None, out=None):
+        """One RFC 8439 ChaCha20 key per row (jj_chacha20_xor): out[i] = data[i, :length] xor the keystream of keys[i] under `nonce` (12 bytes,
+        None = zeros; one nonce for all rows) from block `counter` on (wrapping mod 2^32).  keys (n, 32), data (n, stride): numpy arrays or torch
+        CUDA tensors, mixed freely; length (default: stride) a multiple of 4 in 4..1024, stride a multiple of 4.  Returns (n, length) of data's
+        kind, or `out`; data and out must not overlap."""
+        nonce = _fixed_bytes(nonce, 12, "nonce")
+        for name, x in (("keys", keys), ("data", data)):
+            if not hasattr(x, "shape") or len(x.shape) != 2:
+                raise ValueError("%s: a two-dimensional uint8 array expected" % name)
+        n, stride = data.shape
+        length = stride if length is None else int(length)
+        if tuple(keys.shape) != (n, 32):
+            raise ValueError("keys: shape (%d, 32) expected, got %r" % (n, tuple(keys.shape)))
+        if length < 4 or length > 1024 or length % 4 or stride % 4 or stride < length:
+            raise ValueError("length must be a multiple of 4 in 4..1024 and the row stride a multiple of 4 and at least the length, got %d in %d" % (length, stride))
+        if n * stride > 1 << 32:
+            raise ValueError("at most 2^32 bytes of rows per call")
+        if not 0 <= counter < 1 << 32:
+            raise ValueError("counter: a 32-bit block counter expected")
+        ka, da = _Arg(keys, 32), _Arg(data, None)
+        if out is None:
+            out, optr = self._alloc(da, n, length)
+        else:
+            oa = _Arg(out, None)
+            if oa.n != n * length or oa.torch != da.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x %d bytes of data's kind expected" % (n, length))
+            optr = oa.ptr
+        self._bind_stream([ka, da])
+        self._check(self._lib.jj_chacha20_xor(self._ctx, C.c_size_t(n), ka.ptr, nonce, C.c_uint(counter), da.ptr, C.c_size_t(length), C.c_size_t(stride), optr))
+        return out
+
+    def ka_open(self, sk, P, ct, personal, flags=KA_SAPLING_FLAGS, nonce=None, counter=1, length=None):
+        """Trial decryption: ka_kdf(sk, P, personal, flags), then chacha20_xor of the rows of `ct` with those keys -> (plaintext, ok).  The
+        plaintext of a row whose ok byte is 0 is the row under the all-zero key: ok says which rows mean anything.  With P on the device the
+        keys never visit the host (the cipher reads them on the stream the KDF wrote them on)."""
+        keys, ok = self.ka_kdf(sk, P, personal, flags)
+        return self.chacha20_xor(keys, ct, nonce, counter, length), ok
 
     def msm_finish(self, job):
         """-> the 64-byte affine sum as a numpy array (host memory)."""

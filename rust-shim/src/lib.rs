@@ -262,6 +262,26 @@ impl Gpu {
         assert_eq!(unsafe { jj_sig_challenge(self.0, n, personal.map_or(std::ptr::null(), |p| p.as_ptr() as *const c_void), ptr(r), ptr(a), flat.as_ptr() as _, 0, offsets.as_ptr(), out.as_mut_ptr() as _) }, 0);
         out
     }
+    /// Key agreement with ONE secret scalar and its KDF (`jj_ka_kdf`): `keys[i] = BLAKE2b-256(personal; to_bytes(share_i) [|| p[i]])` with
+    /// `share_i = [sk]P_i` or `[8]([sk]P_i)`; `flags`: the decoder's bits 1 | 2 | 4, 32 = cofactor, 64 = hash the encoding too.  `ok[i] == 0` and a
+    /// zero key where `p[i]` does not decode.  Constant-time in `sk` and in the shares.  `personal`: `None` is sixteen zero bytes (the Sapling
+    /// recipient: `b"Zcash_SaplingKDF"` with flags 1 | 32 | 64).
+    pub fn ka_kdf(&self, sk: &[u8; 32], p: &[[u8; 32]], flags: u32, personal: Option<&[u8; 16]>) -> (Vec<[u8; 32]>, Vec<u8>) {
+        let n = p.len();
+        let mut keys = vec![[0u8; 32]; n];
+        let mut ok = vec![0u8; n];
+        assert_eq!(unsafe { jj_ka_kdf(self.0, n, sk.as_ptr() as _, p.as_ptr() as _, flags, personal.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), keys.as_mut_ptr() as _, ok.as_mut_ptr()) }, 0);
+        (keys, ok)
+    }
+    /// One RFC 8439 ChaCha20 key per row (`jj_chacha20_xor`): rows of `len` bytes at a stride of `in_stride` in `input`, a dense `n x len` result;
+    /// `len` and `in_stride` multiples of 4, `len` in 4..=1024; `nonce`: `None` is twelve zero bytes.
+    pub fn chacha20_xor(&self, keys: &[[u8; 32]], nonce: Option<&[u8; 12]>, counter: u32, input: &[u8], len: usize, in_stride: usize) -> Vec<u8> {
+        let n = keys.len();
+        assert!(n == 0 || input.len() >= (n - 1) * in_stride + len);
+        let mut out = vec![0u8; n * len];
+        assert_eq!(unsafe { jj_chacha20_xor(self.0, n, keys.as_ptr() as _, nonce.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), counter, input.as_ptr() as _, len, in_stride, out.as_mut_ptr() as _) }, 0);
+        out
+    }
     pub fn msm_finish(&self, j: MsmJob) -> AffinePoint {
         let mut out = [0u8; 64];
         assert_eq!(unsafe { jj_msm_finish(j.job, out.as_mut_ptr() as _) }, 0);

@@ -400,9 +400,10 @@ def qbias(p):
     return c
 
 
-def check_mont_ladder(verbose=True):
+def check_mont_ladder(verbose=True, coords=False):
     """k_varbase_mont_x1 and k_varbase_mont (jj_mont.h): the batch inversion of 1 - v, the x-only ladder body iterated to a fixed point
-    (every coordinate of the state is a product), the y-recovery, the map to Edwards and the masked outputs"""
+    (every coordinate of the state is a product), the y-recovery, the map to Edwards and the masked outputs.  coords: return the classes of
+    the recovered U, V and Z, each the join of what varbase_mont_recover can select for it, instead of (state, x1, result)"""
     F = FieldModel(Q)
     ONE, ZERO = F.const(MONT % Q), F.const(0)
     unp = V([0] * NL, [MASK] * (NL - 1) + [(1 << 24) - 1], 0, (1 << 256) - 1)
@@ -471,7 +472,25 @@ def check_mont_ladder(verbose=True):
     F.canon_ok(F.sub(ld, ONE), "mont.is_zero(v - 1)")
     if verbose:
         print("  ladder state: %r\n  x1: %r\n  result: %r" % (st, x1, res))
+    if coords:      # U: the product, -u of the base, 0;  V: the product, v of the base, 1, -1;  Z: the product, 1
+        return dict(u=F.join(F.join(outs[0], outs[3]), ZERO), v=F.join(F.join(F.join(outs[1], ld), ONE), outs[7]), z=F.join(outs[2], ONE))
     return st, x1, res
+
+
+def check_ka_cofactor(verbose=True):
+    """k_varbase_mont_ka<true> (jj_kernels.h): three Curve::dbl behind varbase_mont_recover.  The recovered (U, V, Z) -- products, or the
+    masked-in constants and loaded coordinates: check_mont_ladder's result class -- must lie inside the accumulator class of check_curve.  Its
+    fixed point iterates dbl over every member of that class (the candidates dbl(inv), dbl(inva) of the loop in check_curve), so the doubling
+    of the recovery's output and the doublings of doublings are covered there; Curve::dbl reads u, v and z only."""
+    F, ops, inv, ld = check_curve(verbose=False)
+    res = check_mont_ladder(verbose=False, coords=True)
+    for k in ("u", "v", "z"):
+        assert F.leq(res[k], inv[k]), "recovered coordinate outside the accumulator class acc.%s: %r" % (k, res[k])
+    d = ops["dbl"](dict(inv, **res), "ka.dbl")
+    for k in ("u", "v", "z"):
+        assert F.leq(d[k], inv[k]), "ka.dbl.%s leaves the accumulator class" % k
+    if verbose:
+        print("  recovered point inside the accumulator class; its doubling stays there")
 
 
 def check_field_misc(p, name, verbose=True):
@@ -504,6 +523,8 @@ def main():
     check_kernel_formulas()
     print("Montgomery-form ladder (Fq):")
     check_mont_ladder()
+    print("cofactor doublings behind the Montgomery ladder (jj_ka_kdf):")
+    check_ka_cofactor()
     print("field helpers:")
     check_field_misc(Q, "Fq")
     check_field_misc(RMOD, "Fr")
