@@ -725,6 +725,48 @@ int jj_sig_challenge(jj_ctx*, size_t n, const void* personal16, const void* r32,
 int jj_ka_kdf(jj_ctx*, size_t n, const void* sk32, const void* p32, unsigned flags, const void* personal16, void* key32, uint8_t* ok);
 int jj_chacha20_xor(jj_ctx*, size_t n, const void* keys32, const void* nonce12, unsigned counter, const void* in, size_t len, size_t in_stride, void* out);
 
+/* ---- BLAKE2s-256 over prefix || M_i, and the hash to the curve built on it: a protocol's generators, the diversified base of a note.
+ *   digest_i  = BLAKE2s-256(personal8; prefix || M_i), M_i the msg_len bytes at msgs + i * msg_stride
+ *   jj_blake2s     out32[i] = digest_i
+ *   jj_group_hash  out64[i], ok[i] = byte for byte what jj_decompress writes for digest_i under `flags`: the four JJ_DECOMPRESS_* bits with their
+ *                  meaning there, no other bit; a refused row gets (0, 0) and ok = 0
+ * BLAKE2s as in RFC 7693: unkeyed, 32-byte digest, zero salt, parameter word 0x01010020, the 8 bytes of personalisation in h[6] and h[7].
+ * The library knows NONE of a protocol's personalisations or prefixes, and no message layout or decoding rule: all of them are the caller's
+ * (the group hash of the Zcash protocol specification, GroupHash(D, M) = [8] * decode(BLAKE2s-256(D; URS || M)), is personal8 = D, prefix =
+ * URS, flags = JJ_DECOMPRESS_ZIP216 | JJ_DECOMPRESS_NOT_SMALL_ORDER | JJ_DECOMPRESS_CLEAR_COFACTOR).
+ *   personal8   8 bytes in HOST memory, read before the call returns; NULL = eight zero bytes
+ *   prefix      prefix_len bytes (0..4096) in HOST memory, read before the call returns; NULL only when prefix_len = 0
+ *   msgs        rows of msg_len bytes (0..65536, ONE length per call) at a stride of msg_stride >= msg_len, ANY byte value: rows may begin at
+ *               any byte; NULL only when msg_len = 0;  n * msg_stride <= 2^32;  n <= 2^24
+ *   out32       n x 32 bytes;   out64, ok   n x 64 bytes and n bytes
+ * msgs, the outputs and ok may be host or device pointers, mixed freely (device pointers 16-byte aligned at their base).  n = 0 succeeds and
+ * touches nothing.  JJ_ERR_INVALID, before any device work and with the outputs untouched: a NULL context; a NULL output with n > 0; flag bits
+ * other than the four; a length, stride or count outside the bounds above; a NULL prefix or msgs that would be read; a misaligned device pointer.
+ * Synchronous in the sense of jj_sigverify_each: under the context lock, on the launch stream, in chunks of 2^20 units like jj_ka_kdf; the
+ * digests of jj_group_hash live in a context workspace of 32 bytes per unit of a chunk.  NOTHING has to happen between jj_blake2s with a device
+ * out32 and a later call that reads it.
+ * VARIABLE-TIME over public inputs, like jj_decompress: the decoder behind the hash is that variable-time one, and the block loop runs by the
+ * (public) lengths.
+ * Kernel k_blake2s (jj_blake2s.h), one message per lane, ONE launch per chunk: 32-bit words, the message schedule resolved at compile time so
+ * that h, m and v stay in registers (no scratch), each rotation one v_alignbit_b32, 10 rounds.  The whole blocks of the prefix -- the same for
+ * every lane -- are compressed ONCE on the host, never a block that could be the final one; the kernel gets the midstate, t and the prefix's
+ * tail as arguments.  A lane's message follows the tail at any byte offset and is read as aligned dwords through a funnel shift, never outside
+ * the dwords that hold a byte of its own row.  jj_group_hash then runs the decoder chain of jj_decompress (decompress_dev: k_decompress, the
+ * flag kernels, the shared normaliser, k_mask_outputs) on the chunk's digests as it is.  There is NO fused hash-and-decode kernel: the decoder
+ * is about 2 ms per 2^20 units, one block of this hash below 0.1 ms, and the 64 MB of digest traffic a fused form would save a few tens of
+ * microseconds.
+ * OUT OF SCOPE: ragged message lengths, other digest lengths, keyed or salted BLAKE2s, the rest of a note-commitment check, a jj_multi_* form.
+ * Measured on an MI355X (profiles/group_hash_ab.txt: messages and results on the device, three alternating rounds of one process per route, median;
+ * the old route on a build of the parent commit), a 64-byte prefix with 11-byte messages and the flags of the Zcash group hash: 2^20 rows 2.192 ms per
+ * jj_group_hash call (478 M rows/s) against 2.146 ms for jj_decompress alone on ready digests -- the hash adds 0.047 ms (0.058 ms with 32-byte messages),
+ * as expected before the run: near the traced k_blake2s (0.046 - 0.054 ms) and below the 0.084 ms of k_sig_challenge for one BLAKE2b block -- and
+ * against 105.6 ms for hashlib in 16 processes + jj_decompress (490 ms in one thread); 2^16: 0.688 against 4.71 ms; 2^10: 0.301 against 0.750 ms.
+ * jj_blake2s alone: 0.038 ms per call of 2^20 rows in a full queue (back-to-back calls with device outputs, one synchronisation at the end:
+ * throughput, 27.7 G rows/s, not the latency of one call). */
+int jj_blake2s(jj_ctx*, size_t n, const void* personal8, const void* prefix, size_t prefix_len, const void* msgs, size_t msg_len, size_t msg_stride, void* out32);
+int jj_group_hash(jj_ctx*, size_t n, const void* personal8, const void* prefix, size_t prefix_len, const void* msgs, size_t msg_len, size_t msg_stride, unsigned flags,
+                  void* out64, uint8_t* ok);
+
 /* ---- windowed Pedersen hashes: one launch for n units, every segment in one accumulator.  VARIABLE-TIME (public inputs): the table address
  * depends on the message; a caller with secret inputs composes jj_pedersen_scalars with jj_fixedbase_multi_mul on the LDS tables.
  * A message M is `prefix_bits` bits of `prefix` (low bits first), then up to four fields of the unit's row; every bit is taken LSB-first within

@@ -549,6 +549,28 @@ inline std::vector<uint8_t> chacha20_xor(const Context& c, const std::vector<Byt
   c.check(jj_chacha20_xor(c.raw(), n, keys.data(), nonce ? nonce->data() : nullptr, counter, in.data(), len, in_stride, out.data()));
   return out;
 }
+// BLAKE2s-256(personal; prefix || M_i) for n messages of msg_len bytes, msg_stride apart in `msgs` (jj_blake2s); personal == nullptr is eight
+// zero bytes.  The library knows no protocol's personalisation or prefix: both are the caller's.
+inline std::vector<Bytes32> blake2s(const Context& c, size_t n, const std::vector<uint8_t>& msgs, size_t msg_len, size_t msg_stride, const std::vector<uint8_t>& prefix = {},
+                                    const std::array<uint8_t, 8>* personal = nullptr) {
+  if (n && msg_len && (msg_stride < msg_len || msgs.size() < (n - 1) * msg_stride + msg_len)) throw Error(JJ_ERR_INVALID, "length mismatch");
+  std::vector<Bytes32> out(n);
+  c.check(jj_blake2s(c.raw(), n, personal ? personal->data() : nullptr, prefix.empty() ? nullptr : prefix.data(), prefix.size(), msgs.empty() ? nullptr : msgs.data(), msg_len, msg_stride,
+                     out.data()));
+  return out;
+}
+// Hash to the curve (jj_group_hash): the digest of blake2s decoded exactly as jj_decompress decodes it under `flags` (the four JJ_DECOMPRESS_*
+// bits; JJ_DECOMPRESS_ZIP216 | JJ_DECOMPRESS_NOT_SMALL_ORDER | JJ_DECOMPRESS_CLEAR_COFACTOR is [8] * decode(digest), small order refused).
+// ok[i] = 0 and 64 zero bytes where digest_i is refused.
+struct GroupHash { std::vector<std::array<uint8_t, 64>> points; std::vector<uint8_t> ok; };
+inline GroupHash group_hash(const Context& c, size_t n, const std::vector<uint8_t>& msgs, size_t msg_len, size_t msg_stride, unsigned flags, const std::vector<uint8_t>& prefix = {},
+                            const std::array<uint8_t, 8>* personal = nullptr) {
+  if (n && msg_len && (msg_stride < msg_len || msgs.size() < (n - 1) * msg_stride + msg_len)) throw Error(JJ_ERR_INVALID, "length mismatch");
+  GroupHash r{std::vector<std::array<uint8_t, 64>>(n), std::vector<uint8_t>(n)};
+  c.check(jj_group_hash(c.raw(), n, personal ? personal->data() : nullptr, prefix.empty() ? nullptr : prefix.data(), prefix.size(), msgs.empty() ? nullptr : msgs.data(), msg_len, msg_stride,
+                        flags, r.points.data(), r.ok.data()));
+  return r;
+}
 // MSM cut into parts (jj_msm_partial / jj_msm_combine): part g of G by windows (every part sees all terms) or all windows of a slice
 // of the terms; the records are combined in one host tail
 using MsmRecord = std::array<uint8_t, JJ_MSM_PARTIAL_BYTES>;

@@ -61,6 +61,8 @@ _SIGS.update({
     "jj_sig_challenge": [_sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
     "jj_ka_kdf": [_sz, _vp, _vp, C.c_uint, _vp, _vp, _u8p],
     "jj_chacha20_xor": [_sz, _vp, _vp, C.c_uint, _vp, _sz, _sz, _vp],
+    "jj_blake2s": [_sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp],
+    "jj_group_hash": [_sz, _vp, _vp, _sz, _vp, _sz, _sz, C.c_uint, _vp, _u8p],
     "jj_pedersen_table_create": [C.c_int, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
     "jj_pedersen_hash_vartime": [_vp, _sz, C.c_uint, C.c_int, _vp, _sz, C.c_int, C.POINTER(C.c_uint32), C.c_uint, _vp],
     "jj_pedersen_scalars": [C.c_int, C.c_int, _sz, C.c_uint, C.c_int, _vp, _sz, C.c_int, C.POINTER(C.c_uint32), _vp],

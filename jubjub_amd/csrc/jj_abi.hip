@@ -855,6 +855,77 @@ JJ_API int jj_chacha20_xor(jj_ctx* c, size_t n, const void* keys32, const void* 
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
 }
+// ---- BLAKE2s-256 of prefix || M_i and the hash to the curve built on it (kernel: k_blake2s in jj_kernels.h; jj_blake2s.h):
+// digest_i = BLAKE2s-256(personal8; prefix || M_i), M_i the msg_len bytes at msgs + i * msg_stride; jj_group_hash hands the digests to
+// decompress_dev as it is, so out64 and ok are what jj_decompress writes for them under the same flags.  VARIABLE-TIME over public inputs.
+// Every argument is checked before anything is staged or launched (b2s_plan).  The host compresses the whole blocks of the prefix once
+// (Blake2s::midstate: never a block that could be the final one) and the kernel gets h, t and the prefix's tail as arguments.  The message
+// bytes go through the staging front end as the (n - 1) * msg_stride + msg_len bytes that are read; then per chunk of B2S_CHUNK units, queued
+// one after another on the launch stream: ONE k_blake2s launch, and for jj_group_hash the decoder chain on the chunk's digests, which live in
+// c->b2s (32 bytes per unit of a chunk).  A device out32 is written in launch-stream order, where every other entry point reads its inputs:
+// nothing has to happen between jj_blake2s and a later call.  The library holds no personalisation and no prefix of any protocol.
+constexpr size_t B2S_CHUNK = (size_t)1 << 20;           // units per chunk
+constexpr size_t B2S_PREFIX_MAX = 4096, B2S_MSG_MAX = 65536;
+constexpr unsigned B2S_DECODER_FLAGS = JJ_DECOMPRESS_ZIP216 | JJ_DECOMPRESS_TORSION_FREE | JJ_DECOMPRESS_NOT_SMALL_ORDER | JJ_DECOMPRESS_CLEAR_COFACTOR;
+struct B2sPlan { B2sMid mid; u32 t0, tail_len; size_t msg_bytes; };
+// the checks that need no context, and the plan of a call with n > 0
+static bool b2s_plan(size_t n, const void* personal8, const void* prefix, size_t prefix_len, const void* msgs, size_t msg_len, size_t msg_stride, B2sPlan* p) {
+  if (prefix_len > B2S_PREFIX_MAX || (prefix_len && !prefix) || msg_len > B2S_MSG_MAX || msg_stride < msg_len) return false;
+  if (n > ((size_t)1 << 24) || (msg_stride && n > ((uint64_t)1 << 32) / msg_stride)) return false;        // n * msg_stride <= 2^32
+  if (n == 0) return true;
+  if (msg_len && !msgs) return false;
+  const size_t B = Blake2s::midstate_blocks(prefix_len, msg_len);
+  Blake2s::midstate(p->mid.h, p->mid.tail, (const uint8_t*)personal8, (const uint8_t*)prefix, prefix_len, B);
+  p->t0 = (u32)(Blake2s::BLOCK * B); p->tail_len = (u32)(prefix_len - Blake2s::BLOCK * B);
+  p->msg_bytes = msg_len ? (n - 1) * msg_stride + msg_len : 0;
+  return true;
+}
+static void b2s_launch(jj_ctx* c, size_t n, size_t row0, const B2sPlan& p, const void* dm, size_t msg_len, size_t msg_stride, void* dout32) {
+  hipLaunchKernelGGL(k_blake2s, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, row0, p.mid, p.t0, p.tail_len, (const uint8_t*)dm, (u32)msg_len, msg_stride, dout32);
+}
+JJ_API int jj_blake2s(jj_ctx* c, size_t n, const void* personal8, const void* prefix, size_t prefix_len, const void* msgs, size_t msg_len, size_t msg_stride, void* out32) {
+  if (!c) return JJ_ERR_INVALID;
+  B2sPlan p;
+  if (!b2s_plan(n, personal8, prefix, prefix_len, msgs, msg_len, msg_stride, &p)) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!out32) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  for (const void* q : {p.msg_bytes ? msgs : nullptr, (const void*)out32})
+    if (q && ((uintptr_t)q & 15u) && is_device_ptr(q)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  int rc;
+  const void* dm;
+  OutRef o;
+  if ((rc = stage_in(c, 0, msgs, p.msg_bytes, &dm)) || (rc = stage_out(c, c->out[0], out32, 32 * n, &o))) return rc;
+  for (size_t lo = 0; lo < n; lo += B2S_CHUNK) b2s_launch(c, std::min(B2S_CHUNK, n - lo), lo, p, dm, msg_len, msg_stride, (uint8_t*)o.dev + 32 * lo);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
+JJ_API int jj_group_hash(jj_ctx* c, size_t n, const void* personal8, const void* prefix, size_t prefix_len, const void* msgs, size_t msg_len, size_t msg_stride, unsigned flags,
+                         void* out64, uint8_t* ok) {
+  if (!c) return JJ_ERR_INVALID;
+  if (flags & ~B2S_DECODER_FLAGS) return JJ_ERR_INVALID;
+  B2sPlan p;
+  if (!b2s_plan(n, personal8, prefix, prefix_len, msgs, msg_len, msg_stride, &p)) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!out64 || !ok) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  for (const void* q : {p.msg_bytes ? msgs : nullptr, (const void*)out64, (const void*)ok})
+    if (q && ((uintptr_t)q & 15u) && is_device_ptr(q)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  int rc;
+  const void* dm;
+  OutRef o, k;
+  if ((rc = stage_in(c, 0, msgs, p.msg_bytes, &dm)) || (rc = stage_out(c, c->out[0], out64, 64 * n, &o)) || (rc = stage_out(c, c->okb, ok, n, &k))) return rc;
+  if ((rc = ensure(c, c->b2s, 32 * std::min(n, B2S_CHUNK)))) return rc;
+  for (size_t lo = 0; lo < n; lo += B2S_CHUNK) {
+    const size_t cn = std::min(B2S_CHUNK, n - lo);
+    b2s_launch(c, cn, lo, p, dm, msg_len, msg_stride, c->b2s.p);
+    if ((rc = decompress_dev(c, cn, c->b2s.p, flags, (uint8_t*)o.dev + 64 * lo, (uint8_t*)k.dev + lo, false))) return rc;
+  }
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync)) || (rc = finish_out(c, k, &sync))) return rc;
+  return finish(c, sync);
+}
 // ---- windowed Pedersen hashes (jj_pedersen.h: the function, the table layout, the plan; kernels k_pedersen_gather, k_pedersen_scalars, k_affine_u)
 // sum_i e[i] 16^(chunk0 + i) mod r as canonical bytes, e[i] in +-{1..4}: the positive and the negative digits as two integers, one subtraction
 static void ped_entry_scalar(const int* e, int t, int chunk0, uint8_t out[32]) {

@@ -224,6 +224,8 @@ struct jj_ctx {
   DevBuf sigeach;
   // jj_ka_kdf's workspace of ONE chunk (decoded points, the shares' encodings); launch stream only, like sigseg
   DevBuf ka;
+  // jj_group_hash's workspace of ONE chunk (the 32-byte digests between k_blake2s and the decoder); launch stream only, like sigseg
+  DevBuf b2s;
   bool torsion_ladder = false;   // subgroup test: false = Tate pairing (k_torsion_free), true = multiply by r (reference definition)
   bool fb_const_time = true;     // fixed-base window select: true = lane-staged + ds_bpermute shuffle, false = per-lane LDS gather
   int fb_default_kind = 7;       // what window_bits = 0 means: 7 = signed comb (32 additions + 3 doublings), 6 = signed 6-bit windows (43 additions); JJ_FIXEDBASE_DEFAULT

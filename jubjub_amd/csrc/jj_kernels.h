@@ -1233,6 +1233,33 @@ __global__ void __launch_bounds__(256) k_chacha20_xor(size_t n, const void* keys
   ChaCha20::xor_row(reinterpret_cast<const u32*>(in + i * in_stride), reinterpret_cast<u32*>(out + i * (size_t)nwords * 4), nwords, key, counter, nonce);
 }
 #endif  // JJ_KERNELS_BATCH
+// BLAKE2s-256 of prefix || M_i, one message per lane (jj_blake2s; the hash in front of the decoder in jj_group_hash; jj_blake2s.h):
+// out32[i] = the digest finished from the host's midstate over the prefix's whole blocks (mid.h, t0 bytes absorbed), the prefix's tail
+// (mid.tail, tail_len bytes: the same in every lane, kernel arguments) and the msg_len bytes at msgs + (row0 + i) * msg_stride.  row0 is the
+// chunk's first row: msgs stays the call's 16-byte aligned base whatever the stride, and only the output pointer moves with the chunk.
+// (row0 + i) * msg_stride is below 2^32 for every row of the call (the entry point bounds n * msg_stride), so a lane addresses msgs with 32
+// bits beside the uniform base.  Nothing is read outside the dwords that hold a byte of the lane's own row; 32 bytes are written per lane, as
+// two 16-byte stores.  VARIABLE-TIME over public inputs.
+}  // namespace jj
+#include "jj_blake2s.h"
+namespace jj {
+struct B2sMid { u32 h[8]; u32 tail[16]; };
+#ifdef JJ_KERNELS_BATCH
+__global__ void __launch_bounds__(256) k_blake2s(size_t n, size_t row0, B2sMid mid, u32 t0, u32 tail_len, const uint8_t* msgs, u32 msg_len, size_t msg_stride, void* out32) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u32 pos = (u32)((row0 + i) * msg_stride);
+  u32 w[8];
+  Blake2s::finish(w, mid.h, mid.tail, t0, tail_len, msgs, pos, msg_len);
+  // store8's two vectors, each passed through an empty asm statement as ONE four-register operand: without it the compiler regroups the eight
+  // words that leave the block loop into stores of 12, 16 and 4 bytes, the middle one across a 16-byte boundary
+  typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 lo = {w[0], w[1], w[2], w[3]}, hi = {w[4], w[5], w[6], w[7]};
+  asm volatile("" : "+v"(lo), "+v"(hi));
+  u32x4* p = reinterpret_cast<u32x4*>(static_cast<uint8_t*>(out32) + i * 32);
+  p[0] = lo; p[1] = hi;
+}
+#endif  // JJ_KERNELS_BATCH
 // Windowed Pedersen hashes (jj_pedersen_hash_vartime, jj_pedersen_scalars; table layout, plan and bit extraction: jj_pedersen.h).
 // k_pedersen_gather: one unit per lane and ONE accumulator for all segments -- the walk of k_fixedbase_gather (entries of GNIELS_WORDS,
 // Curve::add_signed<true>, the next window's entry fetched before the current addition), but the digit is the message's own bits: no Fr scalar,

@@ -25,6 +25,9 @@ SAPLING_KDF_PERSONAL = b"Zcash_SaplingKDF"       # the personalisation of the Sa
 FLAG_KA_COFACTOR = 32          # jj_ka_kdf only: share = [8]([sk]P)
 FLAG_KA_HASH_INPUT = 64        # jj_ka_kdf only: hash share || encoding
 KA_SAPLING_FLAGS = FLAG_ZIP216 | FLAG_KA_COFACTOR | FLAG_KA_HASH_INPUT      # the Sapling recipient's ka_kdf flags
+SAPLING_GD_PERSONAL = b"Zcash_gd"                # the personalisation of Sapling's diversified base g_d: a documented example of group_hash's `personal` (the C library does not contain it)
+SAPLING_PH_PERSONAL = b"Zcash_PH"                # the personalisation of Sapling's Pedersen-hash generators: the other example (the protocol's prefix, its URS, is the caller's to supply)
+GROUP_HASH_FLAGS = FLAG_ZIP216 | FLAG_NOT_SMALL_ORDER | FLAG_CLEAR_COFACTOR  # the group hash of the Zcash specification: decode, refuse small order, multiply by 8
 
 
 class JubjubError(RuntimeError):
@@ -320,6 +323,42 @@ def _fixed_bytes(x, size, name):
     if len(x) != size:
         raise ValueError("%s: %d bytes expected, got %d" % (name, size, len(x)))
     return x
+
+
+class _Rows:
+    """An (n, L) uint8 array or CUDA tensor as (pointer, n, L, row stride in bytes) WITHOUT a copy where its rows are contiguous and a fixed
+    number of bytes apart -- a slice buf[:, :L] of a wider array --; any other layout, and a device view whose first byte is not 16-byte
+    aligned, is copied into a contiguous array first (stride = L).  That holds for a single row too: only the row stride, which one row does
+    not have, goes unasked there."""
+
+    def __init__(self, x, name="msgs"):
+        shape = tuple(x.shape) if hasattr(x, "shape") else None
+        if shape is None or len(shape) != 2:
+            raise ValueError("%s: shape (n, L) expected, got %r" % (name, shape))
+        self.n, self.len = int(shape[0]), int(shape[1])
+        empty = self.n == 0 or self.len == 0
+        self.torch = _is_torch(x)
+        if self.torch:
+            import torch
+
+            if x.dtype != torch.uint8:
+                raise TypeError("torch arguments must be uint8")
+            st = tuple(x.stride())
+            # one row has no row stride to ask about; its bytes must still be adjacent and, on the device, its first byte aligned
+            if not (empty or ((self.len == 1 or st[1] == 1) and (self.n == 1 or st[0] >= self.len) and x.data_ptr() % 16 == 0)):
+                x, st = x.clone(memory_format=torch.contiguous_format), (self.len, 1)      # (contiguous() hands a one-row slice back as it is)
+            self.device, self.ptr = x.device, (x.data_ptr() if x.numel() else None)
+        else:
+            if not isinstance(x, np.ndarray):
+                x = _host_bytes(x).reshape(shape)
+            if x.dtype != np.uint8:
+                raise TypeError("numpy arguments must be uint8, got %s" % x.dtype)
+            st = x.strides
+            if not (empty or ((self.len == 1 or st[1] == 1) and (self.n == 1 or st[0] >= self.len))):
+                x, st = np.ascontiguousarray(x), (self.len, 1)
+            self.device, self.ptr = None, (x.ctypes.data if x.size else None)
+        self.stride = self.len if (self.n <= 1 or empty) else int(st[0])
+        self.keep = x
 
 
 class _HostBlock:
@@ -1181,6 +1220,93 @@ class Engine:
         keys never visit the host (the cipher reads them on the stream the KDF wrote them on)."""
         keys, ok = self.ka_kdf(sk, P, personal, flags)
         return self.chacha20_xor(keys, ct, nonce, counter, length), ok
+
+    def _b2s_args(self, msgs, personal, prefix):
+        personal = _fixed_bytes(personal, 8, "personal")
+        prefix = bytes(prefix)
+        if len(prefix) > 4096:
+            raise ValueError("prefix: at most 4096 bytes, got %d" % len(prefix))
+        ma = _Rows(msgs)
+        if ma.len > 65536:
+            raise ValueError("msgs: at most 65536 bytes per message, got %d" % ma.len)
+        if ma.n > 1 << 24 or ma.n * ma.stride > 1 << 32:
+            raise ValueError("at most 2^24 messages and 2^32 bytes of rows per call")
+        return ma, personal, (prefix or None), len(prefix)
+
+    def blake2s(self, msgs, personal=None, prefix=b"", out=None):
+        """BLAKE2s-256(personal; prefix || msgs[i]) for every row (jj_blake2s) -> (n, 32) digests of msgs' kind, or `out`.  msgs: an (n, L)
+        uint8 numpy array or CUDA tensor, L in 0..65536; a view whose rows lie a fixed number of bytes apart (buf[:, :L]) is read where it is,
+        at any byte offset of its rows.  personal: 8 bytes or None for eight zero bytes; prefix: up to 4096 bytes of host memory, the same
+        for every row (its whole blocks are compressed once, on the host).  A device result may be handed straight to any other call: it is
+        written on the stream they read on.  Variable-time over public inputs."""
+        ma, personal, prefix, plen = self._b2s_args(msgs, personal, prefix)
+        if out is None:
+            out, optr = self._alloc(ma, ma.n, 32)
+        else:
+            oa = _Arg(out, 32)
+            if oa.n != ma.n or oa.torch != ma.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x 32 bytes of msgs' kind expected" % ma.n)
+            optr = oa.ptr
+        self._bind_stream([ma])
+        self._check(self._lib.jj_blake2s(self._ctx, C.c_size_t(ma.n), personal, prefix, C.c_size_t(plen), ma.ptr, C.c_size_t(ma.len), C.c_size_t(ma.stride), optr))
+        return out
+
+    def group_hash(self, msgs, personal, prefix=b"", flags=GROUP_HASH_FLAGS, out=None):
+        """Hash to the curve (jj_group_hash) -> (points (n, 64), ok (n,)): the digest of blake2s(msgs, personal, prefix) decoded exactly as
+        decompress(digests, flags) decodes it -- the four FLAG_* decoder bits; the default is the group hash of the Zcash specification,
+        [8] * decode(digest) with small-order results refused --, in one call and without the digests leaving the device.  A refused row
+        gets the point (0, 0) and ok = 0.  The results are of msgs' kind, or `out` = (points, ok).  The library knows no protocol:
+        personalisation, prefix and message layout are the caller's (SAPLING_GD_PERSONAL, SAPLING_PH_PERSONAL are examples)."""
+        ma, personal, prefix, plen = self._b2s_args(msgs, personal, prefix)
+        n = ma.n
+        if out is None:
+            (pts, pptr), (ok, okptr) = self._alloc(ma, n, 64), self._alloc(ma, n, 1)
+        else:
+            pts, ok = out
+            pa, oa = _Arg(pts, 64), _Arg(ok, 1)
+            if pa.n != n or oa.n != n or pa.torch != ma.torch or oa.torch != ma.torch or pa.keep is not pts or oa.keep is not ok:
+                raise ValueError("out: (points, ok), contiguous uint8 arrays of %d x 64 and %d bytes of msgs' kind expected" % (n, n))
+            pptr, okptr = pa.ptr, oa.ptr
+        self._bind_stream([ma])
+        self._check(self._lib.jj_group_hash(self._ctx, C.c_size_t(n), personal, prefix, C.c_size_t(plen), ma.ptr, C.c_size_t(ma.len), C.c_size_t(ma.stride), C.c_uint(flags), pptr, okptr))
+        return pts, ok
+
+    def find_group_hash(self, msgs, personal, prefix=b"", flags=GROUP_HASH_FLAGS):
+        """The first counter at which the group hash exists, for every message -> (points (m, 64), counters (m,) uint8): ONE group_hash call
+        over the 256 m rows msgs[j] || byte(i), i = 0..255, and per message the point of the smallest i with ok = 1 and that i.  msgs: (m, L)
+        uint8, a numpy array or a CUDA tensor; the results are of its kind (device points can go straight into pedersen_table).  Raises
+        JubjubError if a message has no counter with a point: about 47 % of digests decode, so the chance is about 0.53^256 = 2^-234 per message;
+        with FLAG_TORSION_FREE an eighth of those remain and it is about 0.94^256 = 2 * 10^-7, which a caller of many messages may meet."""
+        shape = tuple(msgs.shape) if hasattr(msgs, "shape") else None
+        if shape is None or len(shape) != 2:
+            raise ValueError("msgs: shape (m, L) expected, got %r" % (shape,))
+        m, L = shape
+        if _is_torch(msgs):
+            import torch
+
+            rows = torch.empty((m, 256, L + 1), dtype=torch.uint8, device=msgs.device)
+            rows[:, :, :L] = msgs[:, None, :]
+            rows[:, :, L] = torch.arange(256, dtype=torch.uint8, device=msgs.device)[None, :]
+            pts, ok = self.group_hash(rows.view(m * 256, L + 1), personal, prefix, flags)
+            ok = ok.view(m, 256) != 0
+            first = ok.to(torch.uint8).argmax(dim=1)
+            found = bool(ok.any(dim=1).all().item()) if m else True
+            sel = pts.view(m, 256, 64)[torch.arange(m, device=msgs.device), first] if m else pts.view(0, 64)
+            first = first.to(torch.uint8)
+        else:
+            msgs = _host_bytes(msgs).reshape(m, L)
+            rows = np.empty((m, 256, L + 1), np.uint8)
+            rows[:, :, :L] = msgs[:, None, :]
+            rows[:, :, L] = np.arange(256, dtype=np.uint8)[None, :]
+            pts, ok = self.group_hash(rows.reshape(m * 256, L + 1), personal, prefix, flags)
+            ok = ok.reshape(m, 256) != 0
+            first = ok.argmax(axis=1)
+            found = bool(ok.any(axis=1).all())
+            sel = pts.reshape(m, 256, 64)[np.arange(m), first]
+            first = first.astype(np.uint8)
+        if not found:
+            raise JubjubError("find_group_hash: a message has no counter 0..255 with a point")
+        return sel, first
 
     def msm_finish(self, job):
         """-> the 64-byte affine sum as a numpy array (host memory)."""

@@ -282,6 +282,23 @@ impl Gpu {
         assert_eq!(unsafe { jj_chacha20_xor(self.0, n, keys.as_ptr() as _, nonce.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), counter, input.as_ptr() as _, len, in_stride, out.as_mut_ptr() as _) }, 0);
         out
     }
+    /// `BLAKE2s-256(personal; prefix || M_i)` for `n` messages of `msg_len` bytes, `msg_stride` apart in `msgs` (`jj_blake2s`); `personal`:
+    /// `None` is eight zero bytes.  The library knows no protocol's personalisation or prefix: both are the caller's.
+    pub fn blake2s(&self, n: usize, personal: Option<&[u8; 8]>, prefix: &[u8], msgs: &[u8], msg_len: usize, msg_stride: usize) -> Vec<[u8; 32]> {
+        assert!(n == 0 || msg_len == 0 || (msg_stride >= msg_len && msgs.len() >= (n - 1) * msg_stride + msg_len));
+        let mut out = vec![[0u8; 32]; n];
+        assert_eq!(unsafe { jj_blake2s(self.0, n, personal.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), if prefix.is_empty() { std::ptr::null() } else { prefix.as_ptr() as _ }, prefix.len(), if msgs.is_empty() { std::ptr::null() } else { msgs.as_ptr() as _ }, msg_len, msg_stride, out.as_mut_ptr() as _) }, 0);
+        out
+    }
+    /// Hash to the curve (`jj_group_hash`): the digest of `blake2s` decoded exactly as `jj_decompress` decodes it under `flags` (the decoder's
+    /// bits 1 | 2 | 4 | 8; 1 | 4 | 8 is `[8] * decode(digest)` with small order refused).  `ok[i] == 0` and 64 zero bytes where the digest is refused.
+    pub fn group_hash(&self, n: usize, personal: Option<&[u8; 8]>, prefix: &[u8], msgs: &[u8], msg_len: usize, msg_stride: usize, flags: u32) -> (Vec<[u8; 64]>, Vec<u8>) {
+        assert!(n == 0 || msg_len == 0 || (msg_stride >= msg_len && msgs.len() >= (n - 1) * msg_stride + msg_len));
+        let mut pts = vec![[0u8; 64]; n];
+        let mut ok = vec![0u8; n];
+        assert_eq!(unsafe { jj_group_hash(self.0, n, personal.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), if prefix.is_empty() { std::ptr::null() } else { prefix.as_ptr() as _ }, prefix.len(), if msgs.is_empty() { std::ptr::null() } else { msgs.as_ptr() as _ }, msg_len, msg_stride, flags, pts.as_mut_ptr() as _, ok.as_mut_ptr()) }, 0);
+        (pts, ok)
+    }
     pub fn msm_finish(&self, j: MsmJob) -> AffinePoint {
         let mut out = [0u8; 64];
         assert_eq!(unsafe { jj_msm_finish(j.job, out.as_mut_ptr() as _) }, 0);
