@@ -59,6 +59,13 @@ static int run_batch(jj_ctx* c, size_t n, std::initializer_list<ArgIn> in, std::
   return finish(c, sync);
 }
 
+// f(lo, cn) for every chunk of `chunk` units of n, in order: the bodies whose workspace is bounded by a chunk queue them one after another
+template <class F>
+static int for_chunks(size_t n, size_t chunk, F f) {
+  for (size_t lo = 0; lo < n; lo += chunk) { const int rc = f(lo, std::min(chunk, n - lo)); if (rc) return rc; }
+  return JJ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------- fields
 template <class P, int OP>
 static int field_op(jj_ctx* c, size_t n, const void* a, const void* b, void* out, uint8_t* ok, bool want_ok) {
@@ -187,6 +194,10 @@ static int ladder_workspace(jj_ctx* c, size_t n, size_t lane_words, unsigned* bl
   HIPCHK(c, hipMemsetAsync(c->ws->cursor.p, 0, 8, c->stream));
   return JJ_OK;
 }
+// x1 of n bases batch-inverted into ext, ahead of the Montgomery ladders: a wave takes 64 x MONT_X1_UNITS units
+static void mont_x1_launch(jj_ctx* c, size_t n, const void* dp, SoA ext) {
+  hipLaunchKernelGGL(k_varbase_mont_x1, dim3(blocks_for(64 * ((n + 64 * MONT_X1_UNITS - 1) / (64 * MONT_X1_UNITS)))), dim3(256), 0, c->stream, n, dp, ext);
+}
 // ct: the ladder with the reference's timing discipline (no scalar-dependent address or branch): k_varbase_mont / _ct3 / _ct / _ct_quad; otherwise the
 // per-lane window table in memory (k_varbase / k_varbase_quad: digit-dependent addresses)
 static int varbase_to_ext(jj_ctx* c, size_t n, const void* ds, const void* dp, SoA ext, bool five, bool shared_scalar = false, bool ct = false) {
@@ -195,7 +206,7 @@ static int varbase_to_ext(jj_ctx* c, size_t n, const void* ds, const void* dp, S
     else if (c->vb_ct_window == 3) hipLaunchKernelGGL(k_varbase_ct3, dim3(blocks_for(n)), dim3(256), CT3_LDS_BYTES_PER_BLOCK, c->stream, n, ds, dp, ext);
     else if (c->vb_ct_window == 2) hipLaunchKernelGGL(k_varbase_ct, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, dp, ext);
     else {                                                   // default: the x-only Montgomery ladder, x1 of every base batch-inverted first
-      hipLaunchKernelGGL(k_varbase_mont_x1, dim3(blocks_for(64 * ((n + 64 * MONT_X1_UNITS - 1) / (64 * MONT_X1_UNITS)))), dim3(256), 0, c->stream, n, dp, ext);
+      mont_x1_launch(c, n, dp, ext);
       hipLaunchKernelGGL(k_varbase_mont, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, ds, dp, ext);
     }
     return JJ_OK;
@@ -467,11 +478,20 @@ static int fixedbase_launch(jj_ctx* c, const jj_table* t, size_t n, const void* 
   }
   return JJ_OK;
 }
+// The refusals of a table an entry point cannot use: one of another device, and one of a kind it does not take -- TBL_FIXED: the table of one
+// base or a composite one; TBL_ONE_BASE: the first only (`who` names the entry point in the message); TBL_PEDERSEN: a Pedersen table.
+enum TableKinds { TBL_FIXED, TBL_ONE_BASE, TBL_PEDERSEN };
+static int table_check(jj_ctx* c, const jj_table* t, TableKinds takes, const char* who = "") {
+  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
+  if (takes != TBL_PEDERSEN && t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; }
+  if (takes == TBL_ONE_BASE && t->fx.nb > 0) { c->err = std::string("composite table (jj_fixedbase_composite_create): ") + who + " needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
+  return JJ_OK;
+}
 static int fixedbase_api(jj_ctx* c, const jj_table* t, size_t n, const void* scalars, void* out, int mode) {
   if (!c || !t) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; }
+  int rc;
+  if ((rc = table_check(c, t, TBL_FIXED))) return rc;
   // lanes of the table's kernel: one workgroup per CU for the LDS tables, fb_gather_blocks_per_cu blocks of 256 for the gathered ones
   const size_t fb_lanes = t->window_bits == 7 ? (size_t)c->cus * FBC_THREADS : t->window_bits == FB_W ? (size_t)c->cus * FB_THREADS : (size_t)c->cus * c->fb_gather_blocks_per_cu * 256;
   return run_to_points(c, n, {{scalars, 32, 0}}, out, mode, 3, pipe_chunk_for(c, n, 20, fb_lanes), fb_lanes, [&](size_t cn, const void* const* din, SoA ext) -> int {
@@ -485,8 +505,7 @@ JJ_API int jj_fixedbase_multi_mul(jj_ctx* c, const jj_table* const* tables, int 
   if (!c || !tables || nbases < 1) return JJ_ERR_INVALID;
   for (int j = 0; j < nbases; j++) if (!tables[j]) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  for (int j = 0; j < nbases; j++) if (tables[j]->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  for (int j = 0; j < nbases; j++) { const jj_table* t = tables[j]; if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; } }
+  for (int j = 0; j < nbases; j++) { const int rc = table_check(c, tables[j], TBL_FIXED); if (rc) return rc; }
   return run_to_points(c, n, {{scalars, 32 * (size_t)nbases, 0}}, out64, 0, 5, 0, 0, [&](size_t n, const void* const* din, SoA ext) -> int {
     for (int j = 0; j < nbases; j++) {
       const int chain = (j > 0 ? 1 : 0) | (j + 1 < nbases ? 2 : 0);
@@ -536,8 +555,8 @@ JJ_API int jj_fixedbase_composite_create(jj_ctx* c, int nbases, const void* base
 JJ_API int jj_fixedbase_composite_mul(jj_ctx* c, const jj_table* t, size_t n, const void* scalars, void* out64) {
   if (!c || !t || t->fx.nb < 1) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  int rc = ensure(c, c->ws_tmp[2], 32 * std::max<size_t>(n, 1)); if (rc) return rc;      // the packed scalars; grown ahead of the profile's first mark
+  int rc;
+  if ((rc = table_check(c, t, TBL_FIXED)) || (rc = ensure(c, c->ws_tmp[2], 32 * std::max<size_t>(n, 1)))) return rc;      // the packed scalars; grown ahead of the profile's first mark
   return run_to_points(c, n, {{scalars, 32 * (size_t)t->fx.nb, 0}}, out64, 0, 3, 0, 0, [&](size_t n, const void* const* din, SoA ext) -> int {
     hipLaunchKernelGGL(k_pack_composite, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, din[0], t->fx, c->ws_tmp[2].p);
     return fixedbase_launch(c, t, n, c->ws_tmp[2].p, ext);
@@ -575,9 +594,8 @@ static int fixedvar_api(jj_ctx* c, const jj_table* t, size_t n, const void* a, c
   if (!c || !t) return JJ_ERR_INVALID;
   if (n && (!a || !b || !q || !out)) return JJ_ERR_INVALID;
   JJ_ENTER(c);
-  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; }
-  if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_fixedvar_mul_vartime needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
+  int rc;
+  if ((rc = table_check(c, t, TBL_ONE_BASE, "jj_fixedvar_mul_vartime"))) return rc;
   return run_to_points(c, n, {{a, 32, 0}, {b, 32, 2}, {q, 64, 3}}, out, mode, 5, pipe_chunk_for(c, n, 18), 0, [&](size_t cn, const void* const* din, SoA ext) -> int {      // (the table stays resident)
     return fixedvar_to_ext(c, t, cn, din[0], din[1], din[2], ext);
   });
@@ -725,17 +743,14 @@ JJ_API int jj_sigverify_each(jj_ctx* c, const jj_table* t, size_t n, const void*
   if (n && (!r32 || !a32 || !s32 || !c32 || !verdict)) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   if (flags & ~(unsigned)(JJ_DECOMPRESS_ZIP216 | JJ_SIG_COFACTORLESS)) { c->err = "jj_sigverify_each: flags other than the ZIP-216 bit (1) and the cofactorless bit (16)"; return JJ_ERR_INVALID; }
-  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  if (t->ped.nseg > 0) { c->err = "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it"; return JJ_ERR_INVALID; }
-  if (t->fx.nb > 0) { c->err = "composite table (jj_fixedbase_composite_create): jj_sigverify_each needs the table of one base (jj_fixedbase_table_create)"; return JJ_ERR_INVALID; }
+  int rc;
+  if ((rc = table_check(c, t, TBL_ONE_BASE, "jj_sigverify_each"))) return rc;
   return run_batch(c, n, {{r32, 32, 0}, {a32, 32, 1}, {s32, 32, 2}, {c32, 32, 3}}, {{verdict, 1, &c->okb}}, 0, 0, [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
     const size_t ch = std::min(n, SIG_EACH_CHUNK);
     int rc = ensure(c, c->sigeach, sig_up(128 * ch) + sig_up(2 * ch) + 32 * ch); if (rc) return rc;
-    for (size_t lo = 0; lo < n; lo += SIG_EACH_CHUNK) {
-      const size_t cn = std::min(SIG_EACH_CHUNK, n - lo);
-      if ((rc = sig_each_chunk(c, t, cn, (const uint8_t*)din[0] + 32 * lo, (const uint8_t*)din[1] + 32 * lo, (const uint8_t*)din[2] + 32 * lo, (const uint8_t*)din[3] + 32 * lo, flags, (uint8_t*)dout[0] + lo))) return rc;
-    }
-    return JJ_OK;
+    return for_chunks(n, SIG_EACH_CHUNK, [&](size_t lo, size_t cn) -> int {
+      return sig_each_chunk(c, t, cn, (const uint8_t*)din[0] + 32 * lo, (const uint8_t*)din[1] + 32 * lo, (const uint8_t*)din[2] + 32 * lo, (const uint8_t*)din[3] + 32 * lo, flags, (uint8_t*)dout[0] + lo);
+    });
   });
 }
 // ---- Schnorr challenges hashed on the device (kernel: k_sig_challenge beside the jj_sigverify_each kernels in jj_kernels.h; jj_blake2b.h):
@@ -798,7 +813,7 @@ static int ka_chunk(jj_ctx* c, size_t n, const void* dp, unsigned flags, const u
   if ((rc = decompress_dev(c, n, dp, flags & KA_DECODER_FLAGS, pts, dok, false))) return rc;
   if ((rc = ensure_ext(c, n, 3))) return rc;
   SoA ext = soa_of(c->ws->ext, n);
-  hipLaunchKernelGGL(k_varbase_mont_x1, dim3(blocks_for(64 * ((n + 64 * MONT_X1_UNITS - 1) / (64 * MONT_X1_UNITS)))), dim3(256), 0, c->stream, n, (const void*)pts, ext);
+  mont_x1_launch(c, n, pts, ext);
   if (flags & JJ_KA_COFACTOR) hipLaunchKernelGGL(k_varbase_mont_ka<true>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (const u32*)sk, (const void*)pts, ext);
   else hipLaunchKernelGGL(k_varbase_mont_ka<false>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (const u32*)sk, (const void*)pts, ext);
   if ((rc = normalize_launch(c, n, ext, enc, 1))) return rc;
@@ -820,10 +835,10 @@ JJ_API int jj_ka_kdf(jj_ctx* c, size_t n, const void* sk32, const void* p32, uns
     const size_t ch = std::min(n, KA_CHUNK);
     int rc = ensure(c, c->ka, 256 + sig_up(64 * ch) + 32 * ch); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->ka.p, sk32, 32, is_device_ptr(sk32) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    for (size_t lo = 0; lo < n; lo += KA_CHUNK) {
-      const size_t cn = std::min(KA_CHUNK, n - lo);
-      if ((rc = ka_chunk(c, cn, (const uint8_t*)din[0] + 32 * lo, flags, personal, (uint8_t*)dout[0] + 32 * lo, (uint8_t*)dout[1] + lo))) return rc;
-    }
+    rc = for_chunks(n, KA_CHUNK, [&](size_t lo, size_t cn) -> int {
+      return ka_chunk(c, cn, (const uint8_t*)din[0] + 32 * lo, flags, personal, (uint8_t*)dout[0] + 32 * lo, (uint8_t*)dout[1] + lo);
+    });
+    if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(c->ka.p, 0, 32, c->stream));
     return JJ_OK;
   });
@@ -896,7 +911,7 @@ JJ_API int jj_blake2s(jj_ctx* c, size_t n, const void* personal8, const void* pr
   const void* dm;
   OutRef o;
   if ((rc = stage_in(c, 0, msgs, p.msg_bytes, &dm)) || (rc = stage_out(c, c->out[0], out32, 32 * n, &o))) return rc;
-  for (size_t lo = 0; lo < n; lo += B2S_CHUNK) b2s_launch(c, std::min(B2S_CHUNK, n - lo), lo, p, dm, msg_len, msg_stride, (uint8_t*)o.dev + 32 * lo);
+  (void)for_chunks(n, B2S_CHUNK, [&](size_t lo, size_t cn) -> int { b2s_launch(c, cn, lo, p, dm, msg_len, msg_stride, (uint8_t*)o.dev + 32 * lo); return JJ_OK; });
   bool sync = false;
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
@@ -917,11 +932,11 @@ JJ_API int jj_group_hash(jj_ctx* c, size_t n, const void* personal8, const void*
   OutRef o, k;
   if ((rc = stage_in(c, 0, msgs, p.msg_bytes, &dm)) || (rc = stage_out(c, c->out[0], out64, 64 * n, &o)) || (rc = stage_out(c, c->okb, ok, n, &k))) return rc;
   if ((rc = ensure(c, c->b2s, 32 * std::min(n, B2S_CHUNK)))) return rc;
-  for (size_t lo = 0; lo < n; lo += B2S_CHUNK) {
-    const size_t cn = std::min(B2S_CHUNK, n - lo);
+  rc = for_chunks(n, B2S_CHUNK, [&](size_t lo, size_t cn) -> int {
     b2s_launch(c, cn, lo, p, dm, msg_len, msg_stride, c->b2s.p);
-    if ((rc = decompress_dev(c, cn, c->b2s.p, flags, (uint8_t*)o.dev + 64 * lo, (uint8_t*)k.dev + lo, false))) return rc;
-  }
+    return decompress_dev(c, cn, c->b2s.p, flags, (uint8_t*)o.dev + 64 * lo, (uint8_t*)k.dev + lo, false);
+  });
+  if (rc) return rc;
   bool sync = false;
   if ((rc = finish_out(c, o, &sync)) || (rc = finish_out(c, k, &sync))) return rc;
   return finish(c, sync);
@@ -1004,9 +1019,9 @@ JJ_API int jj_pedersen_hash_vartime(jj_ctx* c, const jj_table* t, size_t n, unsi
   if (!out) return JJ_ERR_INVALID;
   JJ_ENTER(c);
   if (t->ped.nseg < 1) { c->err = "jj_pedersen_hash_vartime needs a table of jj_pedersen_table_create"; return JJ_ERR_INVALID; }
-  if (t->device != c->device) { c->err = "fixed-base table belongs to another device"; return JJ_ERR_INVALID; }
-  if (flags & ~(unsigned)JJ_PEDERSEN_POINT) { c->err = "jj_pedersen_hash_vartime: flags other than the point bit (1)"; return JJ_ERR_INVALID; }
   int rc;
+  if ((rc = table_check(c, t, TBL_PEDERSEN))) return rc;
+  if (flags & ~(unsigned)JJ_PEDERSEN_POINT) { c->err = "jj_pedersen_hash_vartime: flags other than the point bit (1)"; return JJ_ERR_INVALID; }
   if ((rc = ped_check_layout(c, t->ped.nseg, t->ped.seg_chunks, n, prefix_bits, rows, row_stride, nfields, fields))) return rc;
   if (((uintptr_t)out & 15u) && is_device_ptr(out)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
   PedSegs segs; u32 cover;

@@ -75,6 +75,17 @@ def pipelined_entry_points():
     return {fn for fn in bodies if fn.startswith("jj_")} | {fn for fn, body in forwards.items() if body in bodies}
 
 
+def test_shared_pieces_are_written_once():
+    """in jj_abi.hip every refusal of a table an entry point cannot use, the loop over the chunks of a call and the grid of k_varbase_mont_x1
+    stand in one helper each (table_check, for_chunks, mont_x1_launch)"""
+    abi = open(os.path.join(BC.CSRC, "jj_abi.hip")).read()
+    for refusal in ("fixed-base table belongs to another device", "Pedersen table (jj_pedersen_table_create): only jj_pedersen_hash_vartime takes it",
+                    "needs the table of one base (jj_fixedbase_table_create)"):
+        assert abi.count(refusal) == 1, refusal
+    assert len(re.findall(r"for \(size_t lo = 0; lo < n; lo \+= ", abi)) == 1
+    assert abi.count("hipLaunchKernelGGL(k_varbase_mont_x1,") == 1
+
+
 def test_the_table_holds_what_it_must():
     ids = {c.id for c in CASES}
     fns = {c.fn for c in CASES}

@@ -282,3 +282,23 @@ def test_refused_arguments(env, case):
         STATS["calls"] += 1
         STATS["guard_bytes"] += run.counts()[1]
         checked_call(env, case, options, 1, place, MIXED_SKEW)
+
+
+# ---- host and device arrays within one call
+from tests import group_hash_buffer_row, ka_buffer_row  # noqa: E402,F401  (their rows join CASES; ROWS above stays as it was)
+
+MIXED_KINDS = ("jj_fq_add", "jj_varbase_mul2_vartime", "jj_fixedvar_mul_vartime", "jj_decompress", "jj_ka_kdf", "jj_chacha20_xor", "jj_group_hash")
+
+
+@pytest.mark.parametrize("fn", MIXED_KINDS)
+def test_host_and_device_arrays_within_one_call(env, fn):
+    """the arrays of one call alternately in device and in host memory, inputs and outputs alike, starting with either: every array is staged or
+    passed through by its own kind, whatever its neighbours are (the placements of test_host_arenas keep all inputs, and all outputs, on one side)"""
+    case = next(c for c in CASES if c.fn == fn)
+    names = [k for k, _ in case.ins + case.outs]
+    assert len(names) >= 3
+    for first in (0, 1):
+        side = {k: ("dev", "host")[(i + first) % 2] for i, k in enumerate(names)}
+        place = lambda name, role: "dev" if name in case.device else "host" if name in case.host else side[name]      # noqa: E731
+        for n in HOST_SIZES:
+            checked_call(env, case, case.options[0], n, place, MIXED_SKEW)
