@@ -697,8 +697,8 @@ int jj_sig_challenge(jj_ctx*, size_t n, const void* personal16, const void* r32,
  * k_varbase_mont -- ONE unit per lane for every n: there is no quad-of-lanes form, as with jj_varbase_mul2_vartime, so a call of a few units
  * pays the latency of a full ladder --; the shared normaliser writing to_bytes of the share; k_ka_kdf<hash_input>, one unit per lane.
  * k_varbase_mont, its launch and its code are untouched.
- * OUT OF SCOPE: per-unit scalars (the sender's side: jj_varbase_mul_compressed and a hash of the caller's), Poly1305, the note-commitment
- * check that follows a hit, and a _vartime variant.
+ * OUT OF SCOPE: per-unit scalars (the sender's side: jj_varbase_mul_compressed and a hash of the caller's), the note-commitment
+ * check that follows a hit, and a _vartime variant.  (Poly1305 and the tag check that decides a hit: jj_aead_open, below.)
  *
  * jj_chacha20_xor: out[i][j] = in[i * in_stride + j] xor byte j of the ChaCha20 keystream (RFC 8439 section 2.3/2.4: 32-bit block counter,
  * 96-bit nonce) of key keys32[i]; out is n x len, dense.
@@ -724,6 +724,56 @@ int jj_sig_challenge(jj_ctx*, size_t n, const void* personal16, const void* r32,
 #define JJ_KA_HASH_INPUT 64u   /* hash share32 || p32[i] instead of share32 alone */
 int jj_ka_kdf(jj_ctx*, size_t n, const void* sk32, const void* p32, unsigned flags, const void* personal16, void* key32, uint8_t* ok);
 int jj_chacha20_xor(jj_ctx*, size_t n, const void* keys32, const void* nonce12, unsigned counter, const void* in, size_t len, size_t in_stride, void* out);
+
+/* ---- Poly1305 and the ChaCha20-Poly1305 AEAD of RFC 8439, one key per row, the tag checked on the device: the step of a trial decryption
+ * that decides whether there was a hit.
+ *   jj_poly1305   tag16[i] = Poly1305(keys32[i]; the len bytes at in + i * in_stride) (RFC 8439 section 2.5): keys32[i] is the ONE-TIME key,
+ *                 r in bytes 0..15 (clamped by the library), s in bytes 16..31.  tag16 is n x 16, dense
+ *   jj_aead_seal  out[i] = the ciphertext of the len bytes at in + i * in_stride under key keys32[i], followed by its 16-byte tag (section
+ *                 2.8): out is n x (len + 16), dense
+ *   jj_aead_open  the row at in + i * in_stride is len ciphertext bytes followed by the 16 tag bytes.  ok[i] = 1 and out[i] = the len
+ *                 plaintext bytes where the tag verifies; ok[i] = 0 and out[i] = len ZERO bytes where it does not: a failed row never holds
+ *                 plaintext when the call returns.  out is n x len, dense
+ * The AEAD as the RFC has it: the one-time key is the first 32 bytes of ChaCha20 block 0 of (keys32[i], nonce12), the data stream starts at
+ * block 1, the MAC runs over aad || pad16 || ciphertext || pad16 || le64(aad_len) || le64(len).
+ *   nonce12     12 bytes in HOST memory, read before the call returns; NULL = twelve zero bytes.  ONE nonce for all rows
+ *   aad         aad_len <= 64 bytes in HOST memory, read before the call returns, the same for all rows; NULL only with aad_len = 0
+ *   len         a multiple of 4 in 4..1024;  in_stride  a multiple of 4, >= len (jj_poly1305, jj_aead_seal) or >= len + 16 (jj_aead_open);
+ *               n * in_stride <= 2^32;  in and out (tag16) must not overlap: that is checked and refused.  keys32 and ok must not overlap in, out
+ *               or each other either: that is the caller's to keep, as with the neighbouring calls, and is not checked
+ * Any violation (and a NULL context; NULL keys32, in, out, tag16 or ok with n > 0; a misaligned device pointer) returns JJ_ERR_INVALID before
+ * anything is staged or launched, with the outputs untouched.  n = 0 succeeds and touches nothing.  All other pointers may be host or device,
+ * mixed freely (device pointers 16-byte aligned); a host `in` is staged as exactly the bytes that are read, (n - 1) * in_stride + len, plus 16
+ * for jj_aead_open.  Lock and stream rules are those of jj_ka_kdf: NOTHING has to happen between jj_ka_kdf with a device key32 and one of
+ * these calls reading it as keys32 -- both run their kernels on the launch stream, and the keys never have to leave the device.
+ * The Sapling shapes: len 564 in a stride of 580 for a note ciphertext, len 64 in a stride of 80 for an out ciphertext, empty aad, zero nonce.
+ * Both lengths are multiples of 4, which is why the multiple-of-4 rule costs nothing there.
+ * TIMING: neither the instruction stream nor any memory address depends on keys, data, tags or verdicts.  Poly1305 is five 26-bit limbs in
+ * registers, 25 v_mad_u64_u32 per block with 5 r precomputed (jj_poly1305.h shows why no column overflows), its final reduction complete
+ * (h in [p, 2^130) comes out as h - p) and mask-selected; the tag is compared as an OR over the four xored words without an early exit, and the
+ * plaintext words are ANDed with 0 - ok instead of being branched on, so the verdict costs no divergence where nearly every row fails.  Every
+ * loop bound and predicate is a function of len and aad_len, the same in every lane.  tests/test_codegen_aead.py pins this on the gfx950
+ * assembly: no scratch, at most 128 VGPRs, no sub-dword load, no lane-dependent branch or select behind the tag comparison.
+ * Kernels (jj_poly1305.h), ONE launch each, one row per lane, aligned dwords only, the row offset formed in 64 bits, nothing read or written
+ * outside a lane's own row: k_poly1305; k_aead<false> (open: the MAC over the ciphertext first, 16 words loaded per step, then the keystream
+ * pass with the masked store -- the row is read twice); k_aead<true> (seal: the words are absorbed as they are produced).  The aad travels
+ * zero-padded as a kernel argument.
+ * Measured on an MI355X (profiles/aead_ab.txt: device-resident inputs and results, three alternating rounds of one process per route, median):
+ * 2^20 full-note rows (len 564 in a stride of 580): jj_aead_open 1.212 ms, jj_aead_seal 0.860 ms, jj_poly1305 0.582 ms; 2^16 rows: 0.063, 0.057 and
+ * 0.020 ms; 2^10 rows: 0.042, 0.038 and 0.011 ms.  jj_chacha20_xor at the same len and stride on the same build takes 4.488 ms per 2^20 rows
+ * (0.093 at 2^16, 0.050 at 2^10): the call with the MAC and the second read is the faster one.  Supposed cause, not measured: this call issues a
+ * step's 16 loads before the block function, while k_chacha20_xor's assembly alternates load, wait and store (that kernel is left as it is).
+ * Engine.ka_open_aead, jj_ka_kdf then this call: 16.116 ms against 14.439 ms for jj_ka_kdf alone per 2^20 rows (11.6 % over the key agreement),
+ * 1.776 against 1.673 ms at 2^16, 1.293 against 1.246 ms at 2^10.  The host route -- keys and rows copied out, EVP_chacha20_poly1305 of libcrypto
+ * through ctypes -- takes 1675.9 ms with 16 processes and 2995.5 ms in one thread per 2^20 rows, 90.2 ms per 2^16 and 3.2 ms per 2^10: nothing is
+ * BEHIND.  Bytes moved per row over the time: 1521 GB/s for jj_aead_open at 2^20, about a quarter of the 6 TB/s of HBM; the row-per-lane strided
+ * reads look like the limit rather than the arithmetic, which is a supposition from that rate (no counters were read).
+ * OUT OF SCOPE: per-unit scalars on the sender's side, the note-commitment check that follows a hit, per-row nonces or aad, and a len that is
+ * not a multiple of 4. */
+int jj_poly1305(jj_ctx*, size_t n, const void* keys32, const void* in, size_t len, size_t in_stride, void* tag16);
+int jj_aead_open(jj_ctx*, size_t n, const void* keys32, const void* nonce12, const void* aad, size_t aad_len, const void* in, size_t len, size_t in_stride, void* out,
+                 uint8_t* ok);
+int jj_aead_seal(jj_ctx*, size_t n, const void* keys32, const void* nonce12, const void* aad, size_t aad_len, const void* in, size_t len, size_t in_stride, void* out);
 
 /* ---- BLAKE2s-256 over prefix || M_i, and the hash to the curve built on it: a protocol's generators, the diversified base of a note.
  *   digest_i  = BLAKE2s-256(personal8; prefix || M_i), M_i the msg_len bytes at msgs + i * msg_stride

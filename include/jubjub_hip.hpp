@@ -549,6 +549,36 @@ inline std::vector<uint8_t> chacha20_xor(const Context& c, const std::vector<Byt
   c.check(jj_chacha20_xor(c.raw(), n, keys.data(), nonce ? nonce->data() : nullptr, counter, in.data(), len, in_stride, out.data()));
   return out;
 }
+// One Poly1305 one-time key per row (jj_poly1305; r in key bytes 0..15, s in bytes 16..31): the tags of rows of `len` bytes at a stride of
+// in_stride in `in`, n x 16 bytes, dense; len and in_stride multiples of 4, len in 4..1024.
+inline std::vector<uint8_t> poly1305(const Context& c, const std::vector<Bytes32>& keys, const std::vector<uint8_t>& in, size_t len, size_t in_stride) {
+  const size_t n = keys.size();
+  if (n && in.size() < (n - 1) * in_stride + len) throw Error(JJ_ERR_INVALID, "length mismatch");
+  std::vector<uint8_t> out(n * 16);
+  c.check(jj_poly1305(c.raw(), n, keys.data(), in.data(), len, in_stride, out.data()));
+  return out;
+}
+// RFC 8439 ChaCha20-Poly1305 with one key per row, the tag checked on the device (jj_aead_open): a row of `in` is `len` ciphertext bytes and the
+// 16 tag bytes; ok[i] = 1 and the plaintext, or ok[i] = 0 and a zero row where the tag does not verify.  One nonce (nullptr: twelve zero bytes)
+// and one aad (at most 64 bytes) for all rows.
+struct AeadOpened { std::vector<uint8_t> plain; std::vector<uint8_t> ok; };
+inline AeadOpened aead_open(const Context& c, const std::vector<Bytes32>& keys, const std::vector<uint8_t>& in, size_t len, size_t in_stride, const std::vector<uint8_t>& aad = {},
+                            const std::array<uint8_t, 12>* nonce = nullptr) {
+  const size_t n = keys.size();
+  if (n && in.size() < (n - 1) * in_stride + len + 16) throw Error(JJ_ERR_INVALID, "length mismatch");
+  AeadOpened r{std::vector<uint8_t>(n * len), std::vector<uint8_t>(n)};
+  c.check(jj_aead_open(c.raw(), n, keys.data(), nonce ? nonce->data() : nullptr, aad.empty() ? nullptr : aad.data(), aad.size(), in.data(), len, in_stride, r.plain.data(), r.ok.data()));
+  return r;
+}
+// The sealing direction (jj_aead_seal): n x (len + 16) bytes, each row its ciphertext followed by its tag.
+inline std::vector<uint8_t> aead_seal(const Context& c, const std::vector<Bytes32>& keys, const std::vector<uint8_t>& in, size_t len, size_t in_stride, const std::vector<uint8_t>& aad = {},
+                                      const std::array<uint8_t, 12>* nonce = nullptr) {
+  const size_t n = keys.size();
+  if (n && in.size() < (n - 1) * in_stride + len) throw Error(JJ_ERR_INVALID, "length mismatch");
+  std::vector<uint8_t> out(n * (len + 16));
+  c.check(jj_aead_seal(c.raw(), n, keys.data(), nonce ? nonce->data() : nullptr, aad.empty() ? nullptr : aad.data(), aad.size(), in.data(), len, in_stride, out.data()));
+  return out;
+}
 // BLAKE2s-256(personal; prefix || M_i) for n messages of msg_len bytes, msg_stride apart in `msgs` (jj_blake2s); personal == nullptr is eight
 // zero bytes.  The library knows no protocol's personalisation or prefix: both are the caller's.
 inline std::vector<Bytes32> blake2s(const Context& c, size_t n, const std::vector<uint8_t>& msgs, size_t msg_len, size_t msg_stride, const std::vector<uint8_t>& prefix = {},

@@ -61,6 +61,9 @@ _SIGS.update({
     "jj_sig_challenge": [_sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
     "jj_ka_kdf": [_sz, _vp, _vp, C.c_uint, _vp, _vp, _u8p],
     "jj_chacha20_xor": [_sz, _vp, _vp, C.c_uint, _vp, _sz, _sz, _vp],
+    "jj_poly1305": [_sz, _vp, _vp, _sz, _sz, _vp],
+    "jj_aead_open": [_sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _u8p],
+    "jj_aead_seal": [_sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp],
     "jj_blake2s": [_sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp],
     "jj_group_hash": [_sz, _vp, _vp, _sz, _vp, _sz, _sz, C.c_uint, _vp, _u8p],
     "jj_pedersen_table_create": [C.c_int, _vp, C.c_int, C.c_int, C.POINTER(_vp)],

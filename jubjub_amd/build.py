@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libjubjub_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
-COMMON = ["jj_engine.h", "jj_kernels.h", "jj_mont.h", "jj_straus.h", "jj_fixedvar.h", "jj_sig_each.h", "jj_blake2b.h", "jj_blake2s.h", "jj_chacha20.h", "jj_pedersen.h", "jj_curve.h", "jj_field.h", "jj_constants.h", "jj_host_tail.h", "jj_host_tail_ifma.h", os.path.join("..", "..", "include", "jubjub_hip.h")]
+COMMON = ["jj_engine.h", "jj_kernels.h", "jj_mont.h", "jj_straus.h", "jj_fixedvar.h", "jj_sig_each.h", "jj_blake2b.h", "jj_blake2s.h", "jj_chacha20.h", "jj_poly1305.h", "jj_pedersen.h", "jj_curve.h", "jj_field.h", "jj_constants.h", "jj_host_tail.h", "jj_host_tail_ifma.h", os.path.join("..", "..", "include", "jubjub_hip.h")]
 UNITS = {"jj_pipeline": [], "jj_abi": [], "jj_msm": ["jj_msm_kernels.h", "jj_sig_kernels.h", "jj_sig_keyed_kernels.h", "jj_sig_seg_kernels.h"], "jj_multi": []}
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 

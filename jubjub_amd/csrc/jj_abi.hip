@@ -870,6 +870,69 @@ JJ_API int jj_chacha20_xor(jj_ctx* c, size_t n, const void* keys32, const void* 
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
 }
+// ---- Poly1305 and the RFC 8439 ChaCha20-Poly1305 AEAD, one key per row (kernels: k_poly1305, k_aead<seal> in jj_kernels.h; jj_poly1305.h).
+// The bodies are jj_chacha20_xor's: every argument is checked before anything is staged or launched, a host `in` is staged as exactly the
+// bytes that are read, ONE launch over all n rows on the launch stream, no workspace.  nonce12 and aad are host memory and travel as kernel
+// arguments (the aad zero-padded to 64 bytes).  keys32 is read on the launch stream, where jj_ka_kdf wrote it.
+static bool aead_shape_ok(size_t n, size_t len, size_t in_stride, size_t row) {          // row: the bytes of a source row (len, or len + 16)
+  if (len < 4 || len > 1024 || (len & 3u) || (in_stride & 3u) || in_stride < row) return false;
+  return n <= ((uint64_t)1 << 32) / in_stride;                                          // n * in_stride <= 2^32
+}
+JJ_API int jj_poly1305(jj_ctx* c, size_t n, const void* keys32, const void* in, size_t len, size_t in_stride, void* tag16) {
+  if (!c) return JJ_ERR_INVALID;
+  if (!aead_shape_ok(n, len, in_stride, len)) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!keys32 || !in || !tag16) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  const size_t in_bytes = (n - 1) * in_stride + len, out_bytes = 16 * n;
+  if ((uintptr_t)in < (uintptr_t)tag16 + out_bytes && (uintptr_t)tag16 < (uintptr_t)in + in_bytes) { c->err = "jj_poly1305: in and tag16 overlap"; return JJ_ERR_INVALID; }
+  for (const void* p : {keys32, in, (const void*)tag16})
+    if (((uintptr_t)p & 15u) && is_device_ptr(p)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  int rc;
+  const void *dk, *di;
+  OutRef o;
+  if ((rc = stage_in(c, 0, keys32, 32 * n, &dk)) || (rc = stage_in(c, 1, in, in_bytes, &di)) || (rc = stage_out(c, c->out[0], tag16, out_bytes, &o))) return rc;
+  hipLaunchKernelGGL(k_poly1305, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dk, (const uint8_t*)di, (u32)(len / 4), in_stride, o.dev);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
+template <bool SEAL>
+static int aead_call(jj_ctx* c, const char* overlap, size_t n, const void* keys32, const void* nonce12, const void* aad, size_t aad_len, const void* in, size_t len, size_t in_stride,
+                     void* out, uint8_t* ok) {
+  if (!c) return JJ_ERR_INVALID;
+  if (!aead_shape_ok(n, len, in_stride, SEAL ? len : len + 16) || aad_len > 64 || (aad_len && !aad)) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!keys32 || !in || !out || (!SEAL && !ok)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  const size_t in_bytes = (n - 1) * in_stride + len + (SEAL ? 0 : 16), out_bytes = n * (len + (SEAL ? 16 : 0));
+  if ((uintptr_t)in < (uintptr_t)out + out_bytes && (uintptr_t)out < (uintptr_t)in + in_bytes) { c->err = overlap; return JJ_ERR_INVALID; }
+  for (const void* p : {keys32, in, (const void*)out, (const void*)ok})
+    if (p && ((uintptr_t)p & 15u) && is_device_ptr(p)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  uint32_t nonce[3] = {0, 0, 0};
+  if (nonce12) memcpy(nonce, nonce12, 12);
+  AeadAad a;
+  memset(&a, 0, sizeof a);
+  if (aad_len) memcpy(a.w, aad, aad_len);
+  int rc;
+  const void *dk, *di;
+  OutRef o, k = {nullptr, nullptr, 0, false};
+  if ((rc = stage_in(c, 0, keys32, 32 * n, &dk)) || (rc = stage_in(c, 1, in, in_bytes, &di)) || (rc = stage_out(c, c->out[0], out, out_bytes, &o))) return rc;
+  if (!SEAL && (rc = stage_out(c, c->okb, ok, n, &k))) return rc;
+  hipLaunchKernelGGL(k_aead<SEAL>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dk, (u32)nonce[0], (u32)nonce[1], (u32)nonce[2], a, (u32)aad_len, (const uint8_t*)di, (u32)(len / 4),
+                     in_stride, (uint8_t*)o.dev, (uint8_t*)k.dev);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  if (!SEAL && (rc = finish_out(c, k, &sync))) return rc;
+  return finish(c, sync);
+}
+JJ_API int jj_aead_open(jj_ctx* c, size_t n, const void* keys32, const void* nonce12, const void* aad, size_t aad_len, const void* in, size_t len, size_t in_stride, void* out,
+                        uint8_t* ok) {
+  return aead_call<false>(c, "jj_aead_open: in and out overlap", n, keys32, nonce12, aad, aad_len, in, len, in_stride, out, ok);
+}
+JJ_API int jj_aead_seal(jj_ctx* c, size_t n, const void* keys32, const void* nonce12, const void* aad, size_t aad_len, const void* in, size_t len, size_t in_stride, void* out) {
+  return aead_call<true>(c, "jj_aead_seal: in and out overlap", n, keys32, nonce12, aad, aad_len, in, len, in_stride, out, nullptr);
+}
 // ---- BLAKE2s-256 of prefix || M_i and the hash to the curve built on it (kernel: k_blake2s in jj_kernels.h; jj_blake2s.h):
 // digest_i = BLAKE2s-256(personal8; prefix || M_i), M_i the msg_len bytes at msgs + i * msg_stride; jj_group_hash hands the digests to
 // decompress_dev as it is, so out64 and ok are what jj_decompress writes for them under the same flags.  VARIABLE-TIME over public inputs.

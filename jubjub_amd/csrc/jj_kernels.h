@@ -1233,6 +1233,38 @@ __global__ void __launch_bounds__(256) k_chacha20_xor(size_t n, const void* keys
   ChaCha20::xor_row(reinterpret_cast<const u32*>(in + i * in_stride), reinterpret_cast<u32*>(out + i * (size_t)nwords * 4), nwords, key, counter, nonce);
 }
 #endif  // JJ_KERNELS_BATCH
+// Poly1305 and the RFC 8439 AEAD, one key and one row per lane (jj_poly1305, jj_aead_open, jj_aead_seal; jj_poly1305.h).  Addressing is
+// k_chacha20_xor's: aligned dwords only, the byte offset of a row formed in 64 bits, nothing read or written outside the lane's own row.
+// nwords, aad_len and the nonce are the same in every lane: every loop and every predicate is uniform.
+// k_poly1305: tag16[i] = Poly1305(keys32[i]; the 4 * nwords bytes at in + i * in_stride), the one-time key as r (bytes 0..15) and s (16..31).
+// k_aead<false> (open): the row is 4 * nwords ciphertext bytes and 16 tag bytes; writes ok[i] and the dense n x (4 * nwords) plaintext, zeros
+// where the tag does not match -- masked, not branched on.  k_aead<true> (seal): writes the dense n x (4 * nwords + 16) ciphertext and tag.
+}  // namespace jj
+#include "jj_poly1305.h"
+namespace jj {
+#ifdef JJ_KERNELS_BATCH
+__global__ void __launch_bounds__(256) k_poly1305(size_t n, const void* keys32, const uint8_t* in, u32 nwords, size_t in_stride, void* tag16) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 key[8], tag[4];
+  load8(key, keys32, i);
+  Poly1305::mac_row(tag, reinterpret_cast<const u32*>(in + i * in_stride), nwords, key);
+  typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+  *reinterpret_cast<u32x4*>(static_cast<uint8_t*>(tag16) + i * 16) = u32x4{tag[0], tag[1], tag[2], tag[3]};      // 16-byte aligned: one store
+}
+template <bool SEAL>
+__global__ void __launch_bounds__(256) k_aead(size_t n, const void* keys32, u32 nonce0, u32 nonce1, u32 nonce2, AeadAad aad, u32 aad_len, const uint8_t* in, u32 nwords,
+                                              size_t in_stride, uint8_t* out, uint8_t* ok) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 key[8];
+  load8(key, keys32, i);
+  const u32 nonce[3] = {nonce0, nonce1, nonce2};
+  const size_t out_row = (size_t)nwords * 4 + (SEAL ? 16 : 0);
+  const u32 v = Aead::row<SEAL>(reinterpret_cast<const u32*>(in + i * in_stride), reinterpret_cast<u32*>(out + i * out_row), nwords, key, nonce, aad, aad_len);
+  if constexpr (!SEAL) ok[i] = (uint8_t)v;
+}
+#endif  // JJ_KERNELS_BATCH
 // BLAKE2s-256 of prefix || M_i, one message per lane (jj_blake2s; the hash in front of the decoder in jj_group_hash; jj_blake2s.h):
 // out32[i] = the digest finished from the host's midstate over the prefix's whole blocks (mid.h, t0 bytes absorbed), the prefix's tail
 // (mid.tail, tail_len bytes: the same in every lane, kernel arguments) and the msg_len bytes at msgs + (row0 + i) * msg_stride.  row0 is the

@@ -1221,6 +1221,93 @@ class Engine:
         keys, ok = self.ka_kdf(sk, P, personal, flags)
         return self.chacha20_xor(keys, ct, nonce, counter, length), ok
 
+    def _mac_rows(self, keys, data, length, tail):
+        """the shape checks of poly1305, aead_open (tail = 16: the tag behind the row) and aead_seal -> (n, stride, length)"""
+        for name, x in (("keys", keys), ("data", data)):
+            if not hasattr(x, "shape") or len(x.shape) != 2:
+                raise ValueError("%s: a two-dimensional uint8 array expected" % name)
+        n, stride = data.shape
+        length = stride - tail if length is None else int(length)
+        if tuple(keys.shape) != (n, 32):
+            raise ValueError("keys: shape (%d, 32) expected, got %r" % (n, tuple(keys.shape)))
+        if length < 4 or length > 1024 or length % 4 or stride % 4 or stride < length + tail:
+            raise ValueError("length must be a multiple of 4 in 4..1024 and the row stride a multiple of 4 and at least the length%s, got %d in %d"
+                             % (" plus the 16 tag bytes" if tail else "", length, stride))
+        if n * stride > 1 << 32:
+            raise ValueError("at most 2^32 bytes of rows per call")
+        return n, stride, length
+
+    def _mac_out(self, like, out, n, width, name):
+        if out is None:
+            return self._alloc(like, n, width)
+        oa = _Arg(out, None)
+        if oa.n != n * width or oa.torch != like.torch or oa.keep is not out:
+            raise ValueError("%s: a contiguous uint8 array of %d x %d bytes of data's kind expected" % (name, n, width))
+        return out, oa.ptr
+
+    def _aad_bytes(self, aad):
+        aad = bytes(aad or b"")
+        if len(aad) > 64:
+            raise ValueError("aad: at most 64 bytes, got %d" % len(aad))
+        return aad
+
+    def poly1305(self, keys, data, length=None, out=None):
+        """One Poly1305 one-time key per row (jj_poly1305): tags[i] = Poly1305(keys[i]; data[i, :length]), r in key bytes 0..15 and s in bytes
+        16..31 (RFC 8439 section 2.5).  keys (n, 32), data (n, stride): numpy arrays or torch CUDA tensors, mixed freely; length (default:
+        stride) a multiple of 4 in 4..1024, stride a multiple of 4.  Returns (n, 16) of data's kind, or `out`."""
+        n, stride, length = self._mac_rows(keys, data, length, 0)
+        ka, da = _Arg(keys, 32), _Arg(data, None)
+        out, optr = self._mac_out(da, out, n, 16, "out")
+        self._bind_stream([ka, da])
+        self._check(self._lib.jj_poly1305(self._ctx, C.c_size_t(n), ka.ptr, da.ptr, C.c_size_t(length), C.c_size_t(stride), optr))
+        return out
+
+    def aead_open(self, keys, data, nonce=None, aad=b"", length=None, out=None):
+        """RFC 8439 ChaCha20-Poly1305, one key per row, the tag checked on the device (jj_aead_open) -> (plain (n, length), ok (n,)).  A row of
+        data (n, stride) is `length` ciphertext bytes (default: stride - 16) followed by the 16 tag bytes; `nonce` (12 bytes, None = zeros) and
+        `aad` (at most 64 bytes) are the same for all rows.  Where the tag does not verify, ok[i] = 0 and plain[i] is zero: a failed row never
+        holds plaintext.  length a multiple of 4 in 4..1024, stride a multiple of 4 and at least length + 16.  Results of data's kind, or `out`
+        = (plain, ok); data and out must not overlap.  A device result of ka_kdf may be handed over as keys: it is read on the same stream."""
+        nonce, aad = _fixed_bytes(nonce, 12, "nonce"), self._aad_bytes(aad)
+        n, stride, length = self._mac_rows(keys, data, length, 16)
+        ka, da = _Arg(keys, 32), _Arg(data, None)
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError("out: (plain, ok) expected")
+        (plain, pptr), (ok, okptr) = self._mac_out(da, out[0] if out else None, n, length, "out[0]"), self._mac_out(da, out[1] if out else None, n, 1, "out[1]")
+        self._bind_stream([ka, da])
+        self._check(self._lib.jj_aead_open(self._ctx, C.c_size_t(n), ka.ptr, nonce, aad or None, C.c_size_t(len(aad)), da.ptr, C.c_size_t(length), C.c_size_t(stride), pptr, okptr))
+        return plain, ok
+
+    def aead_seal(self, keys, data, nonce=None, aad=b"", length=None, out=None):
+        """RFC 8439 ChaCha20-Poly1305, one key per row (jj_aead_seal): out[i] = the ciphertext of data[i, :length] under keys[i], `nonce` and `aad`
+        followed by its 16-byte tag -> (n, length + 16) of data's kind, or `out`.  length (default: stride) a multiple of 4 in 4..1024, stride a
+        multiple of 4; data and out must not overlap."""
+        nonce, aad = _fixed_bytes(nonce, 12, "nonce"), self._aad_bytes(aad)
+        n, stride, length = self._mac_rows(keys, data, length, 0)
+        ka, da = _Arg(keys, 32), _Arg(data, None)
+        out, optr = self._mac_out(da, out, n, length + 16, "out")
+        self._bind_stream([ka, da])
+        self._check(self._lib.jj_aead_seal(self._ctx, C.c_size_t(n), ka.ptr, nonce, aad or None, C.c_size_t(len(aad)), da.ptr, C.c_size_t(length), C.c_size_t(stride), optr))
+        return out
+
+    def ka_open_aead(self, sk, P, ct, personal, flags=KA_SAPLING_FLAGS, nonce=None, aad=b"", length=None):
+        """Tag-checked trial decryption: ka_kdf(sk, P, personal, flags), then aead_open of the rows of `ct` with those keys -> (plaintext, ok),
+        ok the AND of the two ok arrays.  A row whose P did not decode, or whose tag does not verify, is a zero row with ok = 0.  With P on the
+        device the keys never visit the host.  (A row that did not decode is opened under the all-zero key, which a forged row could satisfy,
+        so the plaintext is multiplied by the combined verdict: no host round trip and no branch on the data.)"""
+        keys, ok = self.ka_kdf(sk, P, personal, flags)
+        plain, tag_ok = self.aead_open(keys, ct, nonce, aad, length)
+        if _is_torch(ok) != _is_torch(tag_ok):                  # P and ct of different kinds: the verdicts are of ct's kind
+            if _is_torch(ok):
+                ok = ok.cpu().numpy()
+            else:
+                import torch
+
+                ok = torch.from_numpy(ok).to(tag_ok.device)
+        both = ok & tag_ok
+        plain *= both[:, None]
+        return plain, both
+
     def _b2s_args(self, msgs, personal, prefix):
         personal = _fixed_bytes(personal, 8, "personal")
         prefix = bytes(prefix)

@@ -282,6 +282,34 @@ impl Gpu {
         assert_eq!(unsafe { jj_chacha20_xor(self.0, n, keys.as_ptr() as _, nonce.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), counter, input.as_ptr() as _, len, in_stride, out.as_mut_ptr() as _) }, 0);
         out
     }
+    /// One Poly1305 one-time key per row (`jj_poly1305`; `r` in key bytes 0..16, `s` in bytes 16..32): the tags of rows of `len` bytes at a
+    /// stride of `in_stride` in `input`, `n x 16` bytes, dense; `len` and `in_stride` multiples of 4, `len` in 4..=1024.
+    pub fn poly1305(&self, keys: &[[u8; 32]], input: &[u8], len: usize, in_stride: usize) -> Vec<[u8; 16]> {
+        let n = keys.len();
+        assert!(n == 0 || input.len() >= (n - 1) * in_stride + len);
+        let mut out = vec![[0u8; 16]; n];
+        assert_eq!(unsafe { jj_poly1305(self.0, n, keys.as_ptr() as _, input.as_ptr() as _, len, in_stride, out.as_mut_ptr() as _) }, 0);
+        out
+    }
+    /// RFC 8439 ChaCha20-Poly1305 with one key per row, the tag checked on the device (`jj_aead_open`): a row of `input` is `len` ciphertext
+    /// bytes and the 16 tag bytes; returns the dense `n x len` plaintext and `ok`, with `ok[i] == 0` and a zero row where the tag does not
+    /// verify.  One `nonce` (`None`: twelve zero bytes) and one `aad` (at most 64 bytes) for all rows.
+    pub fn aead_open(&self, keys: &[[u8; 32]], nonce: Option<&[u8; 12]>, aad: &[u8], input: &[u8], len: usize, in_stride: usize) -> (Vec<u8>, Vec<u8>) {
+        let n = keys.len();
+        assert!(n == 0 || input.len() >= (n - 1) * in_stride + len + 16);
+        let mut out = vec![0u8; n * len];
+        let mut ok = vec![0u8; n];
+        assert_eq!(unsafe { jj_aead_open(self.0, n, keys.as_ptr() as _, nonce.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), if aad.is_empty() { std::ptr::null() } else { aad.as_ptr() as _ }, aad.len(), input.as_ptr() as _, len, in_stride, out.as_mut_ptr() as _, ok.as_mut_ptr()) }, 0);
+        (out, ok)
+    }
+    /// The sealing direction (`jj_aead_seal`): `n x (len + 16)` bytes, each row its ciphertext followed by its tag.
+    pub fn aead_seal(&self, keys: &[[u8; 32]], nonce: Option<&[u8; 12]>, aad: &[u8], input: &[u8], len: usize, in_stride: usize) -> Vec<u8> {
+        let n = keys.len();
+        assert!(n == 0 || input.len() >= (n - 1) * in_stride + len);
+        let mut out = vec![0u8; n * (len + 16)];
+        assert_eq!(unsafe { jj_aead_seal(self.0, n, keys.as_ptr() as _, nonce.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), if aad.is_empty() { std::ptr::null() } else { aad.as_ptr() as _ }, aad.len(), input.as_ptr() as _, len, in_stride, out.as_mut_ptr() as _) }, 0);
+        out
+    }
     /// `BLAKE2s-256(personal; prefix || M_i)` for `n` messages of `msg_len` bytes, `msg_stride` apart in `msgs` (`jj_blake2s`); `personal`:
     /// `None` is eight zero bytes.  The library knows no protocol's personalisation or prefix: both are the caller's.
     pub fn blake2s(&self, n: usize, personal: Option<&[u8; 8]>, prefix: &[u8], msgs: &[u8], msg_len: usize, msg_stride: usize) -> Vec<[u8; 32]> {
