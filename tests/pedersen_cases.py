@@ -39,9 +39,9 @@ def synth_generators(count):
 
 @functools.lru_cache(maxsize=None)
 def generators(name):
-    """affine generators as integer pairs: three distinct prime-order points, or the planted set with P_1 = P_0"""
+    """affine generators as integer pairs: three (or the first two) distinct prime-order points, or the planted set with P_1 = P_0"""
     p = synth_generators(3)
-    return {"three": (p[0], p[1], p[2]), "twin": (p[0], p[0]), "one": (p[1],)}[name]
+    return {"three": (p[0], p[1], p[2]), "two": (p[0], p[1]), "twin": (p[0], p[0]), "one": (p[1],)}[name]
 
 
 def gens_bytes(name):

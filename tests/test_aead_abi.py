@@ -89,6 +89,7 @@ def test_library_exports_the_symbols_and_bindings_name_them():
     for f in (os.path.join("rust-shim", "src", "lib.rs"), os.path.join("include", "jubjub_hip.hpp")):
         src = open(os.path.join(ROOT, f)).read()
         assert "jj_poly1305(" in src and "jj_aead_open(" in src and "jj_aead_seal(" in src, f
+        # the .hpp wrappers are EXECUTED by tests/test_cpp_mirror.py (group aead, on the GPU) and tests/test_cpp_mirror_stub_cpu.py (sizes, strides, NULLs)
 
 
 class _NoCalls:

@@ -77,6 +77,7 @@ def test_library_exports_the_symbols_and_bindings_name_them():
     for f in (os.path.join("rust-shim", "src", "lib.rs"), os.path.join("include", "jubjub_hip.hpp")):
         src = open(os.path.join(ROOT, f)).read()
         assert "jj_ka_kdf(" in src and "jj_chacha20_xor(" in src, f
+        # the .hpp wrappers are EXECUTED by tests/test_cpp_mirror.py (group ka, on the GPU) and tests/test_cpp_mirror_stub_cpu.py (sizes, strides, NULLs)
 
 
 def test_the_c_library_holds_no_protocol_string():

@@ -43,6 +43,7 @@ def test_library_exports_the_symbols_and_bindings_name_them():
         assert hasattr(lib, name) and name in _lib.EXPORTS, name
         assert len(_lib._SIGS[name]) + 1 == len(PROTOS[name]), name                    # the context comes first
         assert "pub fn %s(" % name in ffi and name + "(" in rs and name + "(" in hpp, name
+        # the .hpp wrappers are EXECUTED by tests/test_cpp_mirror.py (group pedersen, on the GPU) and tests/test_cpp_mirror_stub_cpu.py (sizes, nseg, NULLs)
     assert ("pub fn jj_pedersen_hash_vartime(ctx: *mut JjCtx, t: *const JjTable, n: usize, prefix: c_uint, prefix_bits: c_int, rows: *const c_void, row_stride: usize, "
             "nfields: c_int, fields: *const u32, flags: c_uint, out: *mut c_void) -> c_int;") in ffi
     sig = _lib._SIGS["jj_pedersen_hash_vartime"]

@@ -42,6 +42,7 @@ def test_library_exports_the_symbol_and_bindings_name_it():
             "msg_len: usize, offsets: *const u64, c32: *mut c_void) -> c_int;") in ffi
     assert "jj_sig_challenge(" in open(os.path.join(ROOT, "rust-shim", "src", "lib.rs")).read()
     assert "jj_sig_challenge(" in open(os.path.join(ROOT, "include", "jubjub_hip.hpp")).read()
+    # the .hpp wrapper is EXECUTED by tests/test_cpp_mirror.py (group sig, on the GPU) and tests/test_cpp_mirror_stub_cpu.py (offsets, NULLs)
 
 
 def test_the_c_library_holds_no_protocol_string():

@@ -58,6 +58,7 @@ def test_library_exports_the_symbol_and_bindings_name_it():
     assert re.search(r"pub fn jj_sigverify_each\(ctx: \*mut JjCtx, t: \*const JjTable, n: usize,.*verdict: \*mut u8\) -> c_int;", ffi)
     assert "jj_sigverify_each(" in open(os.path.join(ROOT, "rust-shim", "src", "lib.rs")).read()
     assert "jj_sigverify_each(" in open(os.path.join(ROOT, "include", "jubjub_hip.hpp")).read()
+    # the .hpp wrapper is EXECUTED by tests/test_cpp_mirror.py (group sig, on the GPU) and tests/test_cpp_mirror_stub_cpu.py (the flag bits)
 
 
 def test_library_still_reads_no_jj_environment_variable():
