@@ -837,8 +837,9 @@ int jj_group_hash(jj_ctx*, size_t n, const void* personal8, const void* prefix, 
  *   jj_fixedbase_table_destroy.  Every other entry point that takes a jj_table refuses a Pedersen table with JJ_ERR_INVALID.
  * jj_pedersen_hash_vartime
  *   fields   HOST array of 2 * nfields values (byte_offset, nbits), nfields 0..4: field f of unit i is nbits bits from byte
- *            rows + i * row_stride + byte_offset; nbits >= 1, byte_offset + ceil(nbits / 8) <= row_stride; fields may overlap
- *   rows     host or device (16-byte aligned); n * row_stride <= 2^32; may be NULL when nfields = 0
+ *            rows + i * row_stride + byte_offset; nbits >= 1, byte_offset + ceil(nbits / 8) <= row_stride; fields may overlap.  The whole
+ *            range is honoured: byte_offset up to 2^32 - 1 and a field that ends at byte 2^32 of the call's array (row_stride = 2^32, n = 1)
+ *   rows     host or device (16-byte aligned); row_stride <= 2^32 and n * row_stride <= 2^32; may be NULL when nfields = 0
  *   the message (prefix_bits + sum nbits, ONE length per call) must fit 3 * seg_chunks * nseg bits
  *   flags    0: out is n x 32 bytes, the canonical u-coordinate;  JJ_PEDERSEN_POINT: n x 64 affine bytes
  *   JJ_ERR_INVALID before anything is staged or launched, out untouched: a table that is not a Pedersen table, prefix_bits outside 0..32, nfields

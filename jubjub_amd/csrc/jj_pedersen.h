@@ -84,13 +84,17 @@ struct Pedersen {
 // the bytes of a row the fields cover (0 without fields).
 inline std::vector<PedWin> ped_build_plan(int nseg, int c, int w, u32 prefix, int prefix_bits, int nfields, const uint32_t* fields, PedSegs* segs, u32* cover) {
   u32 start[PED_MAX_FIELDS + 1];
-  u32 L = (u32)prefix_bits; *cover = 0;
+  u32 L = (u32)prefix_bits; u64 cov = 0;
   for (int f = 0; f < nfields; f++) {
     start[f] = L; L += fields[2 * f + 1];
-    const u32 end = fields[2 * f] + (fields[2 * f + 1] + 7u) / 8u;
-    if (end > *cover) *cover = end;
+    const u64 end = (u64)fields[2 * f] + ((u64)fields[2 * f + 1] + 7u) / 8u;      // up to 2^32: a 32-bit sum would wrap
+    if (end > cov) cov = end;
   }
   start[nfields] = L;
+  // cover travels as 32 bits.  A cover of exactly 2^32 (row_stride = 2^32, so n = 1 and pos = 0) becomes 0, and last_dword(0, 0) =
+  // (0 - 1) & ~3 = 2^32 - 4 is the dword of the row's byte 2^32 - 1: the arithmetic is modulo 2^32 throughout and only the sum pos + cover - 1,
+  // which is below 2^32 for every row, is used.  Without fields no piece exists and lastd is never looked at.
+  *cover = (u32)cov;
   const u32 chunks = (L + 2u) / 3u, seg_e = ped_seg_entries(c, w);
   std::vector<PedWin> plan;
   for (int j = 0; j <= PED_MAX_SEG; j++) segs->first[j] = 0;
@@ -112,8 +116,11 @@ inline std::vector<PedWin> ped_build_plan(int nseg, int c, int w, u32 prefix, in
       for (int f = 0; f < nfields; f++) {
         const u32 lo = std::max(b0, start[f]), hi = std::min(b1, start[f + 1]);
         if (lo >= hi) continue;
-        const u32 bit = 8u * fields[2 * f] + (lo - start[f]);
-        x.pc[x.np++] = PedPiece{bit >> 3, bit & 7u, (1u << (hi - lo)) - 1u, lo - b0};
+        // the piece's first bit within the field.  byte_offset + rel / 8 < 2^32 since the field ends inside row_stride <= 2^32; the bit number
+        // 8 * byte_offset + rel would not fit 32 bits from byte_offset = 2^29 on
+        const u32 rel = lo - start[f];
+        x.pc[x.np++] = PedPiece{fields[2 * f] + (rel >> 3), rel & 7u, (1u << (hi - lo)) - 1u, lo - b0};
+
       }
       plan.push_back(x);
     }

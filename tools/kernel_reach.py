@@ -16,6 +16,8 @@ tests/kernel_reach.json and tests/kernel_reach_ledger.json are the ledgers of ea
       with one demangler (llvm-cxxfilt of the ROCm toolchain, c++filt where that is not installed), `.kd` stripped -- and writes profiles/kernel_reach_ledger.json.  A traced jj kernel that no compiled
       kernel matches is an error.
   python tools/kernel_reach.py DIR                                                   both in turn
+  python tools/kernel_reach.py --add DIR                                             no GPU: a new GPU test file that adds no kernel -- the files
+      traced into DIR (--trace DIR --files test_gpu_new.py) enter the committed ledger, every other file's entries and the header stay
   python tools/kernel_reach.py --check                                               no GPU: the committed ledger as a table
 """
 import argparse
@@ -236,6 +238,39 @@ def build_ledger(outdir, asm=None):
     return kernels
 
 
+def add_to_ledger(outdir):
+    """--add: the per-file results in outdir replace those files' entries in the committed ledger; every other file's counts, and the header of
+    the full trace, stay.  For a change that adds a GPU test file and no kernel: the compiled names must be the ledger's."""
+    ledger = json.load(open(LEDGER))
+    kernels = ledger["kernels"]
+    for path in sorted(glob.glob(os.path.join(outdir, "test_gpu_*.json"))):
+        rec = json.load(open(path))
+        if rec["untraced_rc"] or rec["traced_rc"]:
+            raise SystemExit("%s did not pass while traced (untraced rc %d, traced rc %d); the ledger is not written" % (rec["file"], rec["untraced_rc"], rec["traced_rc"]))
+        for e in kernels.values():
+            e["files"].pop(rec["file"], None)
+        raws = sorted(rec["kernels"])
+        for raw, name in zip(raws, canonical_all(raws)):
+            if not name.startswith("jj::"):
+                continue
+            if name not in kernels:
+                raise SystemExit("%s launched %s, which the ledger does not name: trace every file again" % (rec["file"], name))
+            cnt, lo, hi = rec["kernels"][raw]
+            e = kernels[name]
+            e["files"][rec["file"]] = e["files"].get(rec["file"], 0) + cnt
+            size = lambda s: int(s.split(" x ")[0])      # noqa: E731
+            if not e["smallest"] or lo[0] < size(e["smallest"]):
+                e["smallest"] = "%d x %d" % tuple(lo)
+            if not e["largest"] or hi[0] > size(e["largest"]):
+                e["largest"] = "%d x %d" % tuple(hi)
+        ledger["seconds"][rec["file"]] = {"untraced_s": rec["untraced_s"], "traced_s": rec["traced_s"]}
+    missing = [f for f in gpu_files() if f not in ledger["seconds"]]
+    if missing:
+        raise SystemExit("no trace of: " + ", ".join(missing))
+    write_ledger(ledger)
+    return kernels
+
+
 def write_ledger(ledger, path=None):
     """sorted keys, one kernel per line"""
     path = path or LEDGER
@@ -270,12 +305,16 @@ def main():
     ap.add_argument("dir", nargs="?", help="directory of the per-file results (both phases in turn)")
     ap.add_argument("--trace", metavar="DIR")
     ap.add_argument("--ledger", metavar="DIR")
+    ap.add_argument("--add", metavar="DIR", help="no GPU: put the files traced into DIR (--trace DIR --files ...) into the committed ledger, the other files' entries kept")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--files", default="", help="comma-separated subset of the GPU test files (a long suite is traced over several calls into one DIR)")
     ap.add_argument("--untraced-limit", type=int, default=600, help="seconds allowed to a file's untraced run")
     a = ap.parse_args()
     if a.check:
         return check()
+    if a.add:
+        add_to_ledger(a.add)
+        return 0
     files = [f for f in a.files.split(",") if f] or gpu_files()
     assert all(f in gpu_files() for f in files), files
     if a.trace or a.dir:
