@@ -864,6 +864,49 @@ int jj_pedersen_hash_vartime(jj_ctx*, const jj_table* t, size_t n, unsigned pref
 int jj_pedersen_scalars(jj_ctx*, int nseg, int seg_chunks, size_t n, unsigned prefix, int prefix_bits,
                         const void* rows, size_t row_stride, int nfields, const uint32_t* fields, void* scalars32);
 
+/* ---- windowed Pedersen commitment over several row arrays:  out[i] = H(M_i) + [r_i] R  in one call.  VARIABLE-TIME in the message.
+ * H is exactly the function of jj_pedersen_hash_vartime over `ped` (a table of jj_pedersen_table_create, any window_chunks).  M_i is prefix_bits
+ * bits of `prefix` (low bits first), then up to four fields; field f is nbits bits from byte srcs[src] + i * strides[src] + byte_offset, LSB-first
+ * within a byte.  Fields come in the order given, which need not be source order; a source may serve several fields; fields may overlap.
+ *   ped      a Pedersen table;  rbase  the table of ONE base R, any table jj_fixedvar_mul_vartime accepts (every window_bits; a composite or a
+ *            Pedersen table is refused);  r32  n x 32 raw bytes, read exactly as jj_fixedbase_mul reads its scalars (the low 252 bits)
+ *   rbase == NULL together with r32 == NULL: the plain multi-source hash (with nsrc = 1 the bytes of jj_pedersen_hash_vartime); exactly one of
+ *            the two being NULL is refused
+ *   srcs, strides   HOST arrays of nsrc pointers / byte strides, nsrc 1..4 (0 only with nfields = 0); every source host or device (16-byte
+ *            aligned), mixed freely; strides[s] <= 2^32 and n * strides[s] <= 2^32.  A host source is read up to the last byte its fields cover
+ *            in its last row, a device source up to the end of the aligned dword of that byte
+ *   fields   HOST array of 3 * nfields values (src, byte_offset, nbits), nfields 0..4: src < nsrc, nbits >= 1,
+ *            byte_offset + ceil(nbits / 8) <= strides[src]; the message must fit 3 * seg_chunks * nseg bits; prefix_bits 0..32
+ *   flags    0: out is n x 32 bytes, the canonical u-coordinate (Extract of the Zcash specification);  JJ_PEDERSEN_POINT: n x 64 affine bytes;
+ *            any other bit is refused
+ * The contract: for every kind of rbase every unit equals, byte for byte, the composed route on rows packed by the caller,
+ *     jj_point_add(jj_pedersen_hash_vartime(.., JJ_PEDERSEN_POINT) on the packed rows, jj_fixedbase_mul(rbase, r)).
+ * The Edwards law is complete: H(M) = -[r]R gives the identity (u = 0 in the u-only form), H(M) = [r]R takes no special path.
+ * Every limit above is refused with JJ_ERR_INVALID before anything is staged or launched, out untouched; so are a table of another device and a
+ * misaligned device pointer.  n = 0 succeeds and touches nothing.  The lock and stream rules are those of jj_pedersen_hash_vartime.
+ * Kernel k_pedersen_commit (jj_kernels.h), beside k_pedersen_gather: one unit per lane, one accumulator; a piece of the host-made plan names
+ * its source, the lane forms its row position and the clamp dword per source, and the funnel-shift rule of jj_pedersen_hash_vartime holds for
+ * each source separately.  What depends on r:
+ *   gathered rbase (window_bits 8..16)  the same kernel goes on in the same registers with the walk of k_fixedbase_gather (the recode addition,
+ *       ceil(253 / w) signed entries, the first fetched before the message's last addition): VARIABLE-TIME in r as well
+ *   LDS rbase (window_bits 6, 7, the default)  the kernel stops after the message and the table's own kernel finishes on the accumulator it left
+ *       (the shape of jj_fixedvar_mul_vartime's LDS route): the blinding term is CONSTANT-TIME in r
+ * Then the shared normaliser once, and k_affine_u for the u-only form.  No scratch.
+ * NOT MEASURED YET: tools/commit_ab.py is written and its routes are held to the restatement, but profiles/commit_ab.txt does not exist --
+ * the fused walk ships for gathered tables on the expectation alone 
+ * (the shipped figures: 2.36 ms per 2^20 for the 576-bit four-segment hash, about 0.9 ms for a gathered fixed-base walk, so about 3 ms fused against about 4 ms composed), 
+ * and the project's rule (fused only if ahead of the two-launch form by more than the larger range; BEHIND written where a size is behind) is still to be applied to a run.
+ * Real hits are rare: the rate of this check matters for rescans and for callers who check every output they created.
+ * The library knows no protocol.  The documented example is a note commitment: ped of four segments of 63 chunks, prefix 0b111111 (6 bits),
+ * fields {0, value_offset, 64,  1, 0, 256,  2, 0, 256} over the plaintext rows, repr(g_d) and repr(pk_d): 582 bits, 194 chunks.
+ * OUT OF SCOPE: a constant-time message term (compose jj_pedersen_scalars with jj_fixedbase_multi_mul), multi-source jj_pedersen_scalars,
+ * compaction of hit rows, a jj_multi_* form. */
+int jj_pedersen_commit_vartime(jj_ctx*, const jj_table* ped, const jj_table* rbase, size_t n,
+                               unsigned prefix, int prefix_bits,
+                               int nsrc, const void* const* srcs, const size_t* strides,
+                               int nfields, const uint32_t* fields /* triples (src, byte_offset, nbits) */,
+                               const void* r32, unsigned flags, void* out);
+
 /* ---- encodings----------------------------------------------------------------------------------------- */
 #define JJ_DECOMPRESS_ZIP216          1u  /* reject the two non-canonical encodings (src/lib.rs:469-471, 522-531) */
 #define JJ_DECOMPRESS_TORSION_FREE    2u  /* additionally require [r]P = O  (SubgroupPoint::from_bytes, lib.rs:1427-1429) */

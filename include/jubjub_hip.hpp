@@ -307,9 +307,40 @@ class PedersenTable {
     c_->check(jj_pedersen_scalars(c_->raw(), nseg_, seg_chunks_, n, prefix, prefix_bits, rows.data(), row_stride, (int)fields.size(), fields.empty() ? nullptr : fields[0].data(), out.data()));
     return out;
   }
+  // H(M) + [r] R per unit (jj_pedersen_commit_vartime): the message's fields (src, byte_offset, nbits) lie in up to four row arrays, sources[s]
+  // holding n rows of strides[s] bytes; R is the base of `rbase`, r one scalar per unit.  rbase = nullptr with an empty r: the plain hash, n
+  // units.  -> canonical u-coordinates.  VARIABLE-TIME in the message; r is constant-time with an LDS table (FixedBase's default).
+  std::vector<Bytes32> commit(const FixedBase* rbase, const std::vector<std::vector<uint8_t>>& sources, const std::vector<size_t>& strides,
+                              const std::vector<std::array<uint32_t, 3>>& fields, const std::vector<Bytes32>& r, size_t n = 0, unsigned prefix = 0, int prefix_bits = 0) const {
+    std::vector<Bytes32> out(commit_units(rbase, sources, strides, r, n));
+    commit_call(rbase, sources, strides, fields, r, out.size(), prefix, prefix_bits, 0, out.data());
+    return out;
+  }
+  AffineBatch commit_points(const FixedBase* rbase, const std::vector<std::vector<uint8_t>>& sources, const std::vector<size_t>& strides,
+                            const std::vector<std::array<uint32_t, 3>>& fields, const std::vector<Bytes32>& r, size_t n = 0, unsigned prefix = 0, int prefix_bits = 0) const {
+    std::vector<Bytes64> out(commit_units(rbase, sources, strides, r, n));
+    commit_call(rbase, sources, strides, fields, r, out.size(), prefix, prefix_bits, JJ_PEDERSEN_POINT, out.data());
+    return AffineBatch(*c_, std::move(out));
+  }
   const jj_table* raw() const { return t_; }
 
  private:
+  // the units of a commit call: r's length with a blinding term, else `n`; every source must hold that many rows
+  size_t commit_units(const FixedBase* rbase, const std::vector<std::vector<uint8_t>>& sources, const std::vector<size_t>& strides, const std::vector<Bytes32>& r, size_t n) const {
+    if (!rbase && !r.empty()) throw Error(JJ_ERR_INVALID, "r without rbase");
+    if (sources.size() != strides.size() || sources.size() > 4) throw Error(JJ_ERR_INVALID, "sources / strides mismatch");
+    const size_t units = rbase ? r.size() : n;
+    for (size_t s = 0; s < sources.size(); s++)
+      if (sources[s].size() < units * strides[s]) throw Error(JJ_ERR_INVALID, "a source holds fewer rows than there are units");
+    return units;
+  }
+  void commit_call(const FixedBase* rbase, const std::vector<std::vector<uint8_t>>& sources, const std::vector<size_t>& strides, const std::vector<std::array<uint32_t, 3>>& fields,
+                   const std::vector<Bytes32>& r, size_t n, unsigned prefix, int prefix_bits, unsigned flags, void* out) const {
+    std::vector<const void*> ptrs;
+    for (const auto& s : sources) ptrs.push_back(s.data());
+    c_->check(jj_pedersen_commit_vartime(c_->raw(), t_, rbase ? rbase->raw() : nullptr, n, prefix, prefix_bits, (int)sources.size(), ptrs.data(), strides.data(), (int)fields.size(),
+                                         fields.empty() ? nullptr : fields[0].data(), rbase ? r.data() : nullptr, flags, out));
+  }
   const Context* c_;
   int nseg_, seg_chunks_;
   jj_table* t_ = nullptr;

@@ -69,6 +69,7 @@ _SIGS.update({
     "jj_pedersen_table_create": [C.c_int, _vp, C.c_int, C.c_int, C.POINTER(_vp)],
     "jj_pedersen_hash_vartime": [_vp, _sz, C.c_uint, C.c_int, _vp, _sz, C.c_int, C.POINTER(C.c_uint32), C.c_uint, _vp],
     "jj_pedersen_scalars": [C.c_int, C.c_int, _sz, C.c_uint, C.c_int, _vp, _sz, C.c_int, C.POINTER(C.c_uint32), _vp],
+    "jj_pedersen_commit_vartime": [_vp, _vp, _sz, C.c_uint, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(_sz), C.c_int, C.POINTER(C.c_uint32), _vp, C.c_uint, _vp],
     "jj_msm_partial": [_sz, _vp, _vp, C.c_int, C.c_int, _vp],
     "jj_msm_combine_dev": [_sz, _vp, _vp],
     "jj_ctx_set_comm": [_vp, C.c_int, C.c_int, _vp],

@@ -1128,6 +1128,82 @@ JJ_API int jj_pedersen_scalars(jj_ctx* c, int nseg, int seg_chunks, size_t n, un
   if ((rc = finish_out(c, o, &sync))) return rc;
   return finish(c, sync);
 }
+// ---- windowed Pedersen commitment over several row arrays: out[i] = H(M_i) + [r_i] R (k_pedersen_commit; the contract: include/jubjub_hip.h).
+// Staging slots: sources 0..2 in c->in[0..2], the plan in c->in[3] (as the hash), source 3 in c->in[4], r in c->in[5].
+static const int PED_COMMIT_SRC_SLOT[PED_MAX_SRC] = {0, 1, 2, 4};
+// JJ_COMMIT_PROBE_SPLIT (experiments only, the same results): a gathered rbase takes the two launches of the LDS tables -- k_pedersen_commit up to
+// the message's end, then k_fixedbase_gather with chain = 1 -- which is what the fused walk has to beat (tools/commit_ab.py, profiles/commit_ab.txt)
+#if defined(JJ_COMMIT_PROBE_SPLIT) && !defined(JJ_EXPERIMENTS)
+#error "JJ_COMMIT_PROBE_SPLIT needs -DJJ_EXPERIMENTS: the shipped library is built with the defaults"
+#endif
+#ifdef JJ_COMMIT_PROBE_SPLIT
+constexpr bool COMMIT_FUSED = false;
+#else
+constexpr bool COMMIT_FUSED = true;
+#endif
+JJ_API int jj_pedersen_commit_vartime(jj_ctx* c, const jj_table* ped, const jj_table* rbase, size_t n, unsigned prefix, int prefix_bits, int nsrc, const void* const* srcs,
+                                      const size_t* strides, int nfields, const uint32_t* fields, const void* r32, unsigned flags, void* out) {
+  if (!c || !ped) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!out) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  const char* who = "jj_pedersen_commit_vartime";
+  if (ped->ped.nseg < 1) { c->err = "jj_pedersen_commit_vartime needs a table of jj_pedersen_table_create"; return JJ_ERR_INVALID; }
+  int rc;
+  if ((rc = table_check(c, ped, TBL_PEDERSEN))) return rc;
+  if ((rbase == nullptr) != (r32 == nullptr)) { c->err = "jj_pedersen_commit_vartime: rbase and r32 are both given or both NULL (the hash-only form)"; return JJ_ERR_INVALID; }
+  if (rbase && (rc = table_check(c, rbase, TBL_ONE_BASE, who))) return rc;
+  if (flags & ~(unsigned)JJ_PEDERSEN_POINT) { c->err = "jj_pedersen_commit_vartime: flags other than the point bit (1)"; return JJ_ERR_INVALID; }
+  if (prefix_bits < 0 || prefix_bits > 32) { c->err = "Pedersen commit: prefix_bits must be 0..32"; return JJ_ERR_INVALID; }
+  if (nfields < 0 || nfields > PED_MAX_FIELDS) { c->err = "Pedersen commit: nfields must be 0..4"; return JJ_ERR_INVALID; }
+  if (nsrc < 0 || nsrc > PED_MAX_SRC || (nsrc == 0 && nfields > 0)) { c->err = "Pedersen commit: nsrc must be 1..4 (0 only without fields)"; return JJ_ERR_INVALID; }
+  if ((nfields && (!fields || is_device_ptr(fields))) || (nsrc && (!srcs || !strides || is_device_ptr(srcs) || is_device_ptr(strides)))) {
+    c->err = "Pedersen commit: srcs, strides and fields must be host arrays"; return JJ_ERR_INVALID;
+  }
+  for (int s = 0; s < nsrc; s++) {
+    if (!srcs[s]) { c->err = "Pedersen commit: NULL source"; return JJ_ERR_INVALID; }
+    if ((uint64_t)strides[s] > ((uint64_t)1 << 32) || (uint64_t)n * strides[s] > ((uint64_t)1 << 32)) { c->err = "Pedersen commit: more than 2^32 bytes of rows in one source"; return JJ_ERR_INVALID; }
+    if (((uintptr_t)srcs[s] & 15u) && is_device_ptr(srcs[s])) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  }
+  uint64_t bits = (uint64_t)prefix_bits, cov[PED_MAX_SRC] = {0, 0, 0, 0};
+  for (int f = 0; f < nfields; f++) {
+    const uint64_t s = fields[3 * f], off = fields[3 * f + 1], nb = fields[3 * f + 2];
+    if (s >= (uint64_t)nsrc) { c->err = "Pedersen commit: a field names a source that is not there"; return JJ_ERR_INVALID; }
+    if (nb < 1 || off + (nb + 7) / 8 > (uint64_t)strides[s]) { c->err = "Pedersen commit: a field is empty or reaches past its source's stride"; return JJ_ERR_INVALID; }
+    cov[s] = std::max(cov[s], off + (nb + 7) / 8);
+    bits += nb;
+  }
+  if (bits > 3ull * (uint64_t)ped->ped.seg_chunks * (uint64_t)ped->ped.nseg) { c->err = "Pedersen commit: the message is longer than 3 * seg_chunks * nseg bits"; return JJ_ERR_INVALID; }
+  if ((((uintptr_t)out & 15u) && is_device_ptr(out)) || (r32 && ((uintptr_t)r32 & 15u) && is_device_ptr(r32))) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  PedSegs segs; PedSrcs S; memset(&S, 0, sizeof S);
+  const std::vector<PedWinSrc> plan = ped_build_plan_src(ped->ped.nseg, ped->ped.seg_chunks, ped->ped.window_chunks, prefix, prefix_bits, nfields, fields, &segs, S.cover);
+  const bool point = (flags & JJ_PEDERSEN_POINT) != 0;
+  const int mode = !rbase ? PED_COMMIT_HASH : (rbase->window_bits >= 8 && COMMIT_FUSED) ? PED_COMMIT_FUSED : PED_COMMIT_CHAIN;
+  const void *dplan, *dr = nullptr;
+  OutRef o;
+  if ((rc = ensure_ext(c, n, mode == PED_COMMIT_CHAIN ? 5 : 3)) || (!point && (rc = ensure(c, c->ws_tmp[2], 64 * n)))) return rc;
+  for (int s = 0; s < nsrc; s++) {
+    // a host source is staged up to the last covered byte of its last row: a row-strided view ends there.  A source no field reads is not read.
+    const void* d;
+    if ((rc = stage_in(c, PED_COMMIT_SRC_SLOT[s], srcs[s], cov[s] ? (n - 1) * strides[s] + (size_t)cov[s] : 0, &d))) return rc;
+    S.rows[s] = (const uint8_t*)d; S.stride[s] = (u32)strides[s];
+  }
+  if ((rc = stage_in(c, 3, plan.data(), plan.size() * sizeof(PedWinSrc), &dplan)) || (rbase && (rc = stage_in(c, 5, r32, 32 * n, &dr))) ||
+      (rc = stage_out(c, c->out[0], out, (point ? 64 : 32) * n, &o))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  prof_mark(c, 0);
+  const unsigned gblocks = (unsigned)std::min((size_t)c->cus * c->fb_gather_blocks_per_cu, (n + 255) / 256);
+  hipLaunchKernelGGL(k_pedersen_commit, dim3(gblocks), dim3(256), 0, c->stream, n, S, (const PedWinSrc*)dplan, (int)plan.size(), (const u32*)ped->dev, dr,
+                     mode == PED_COMMIT_FUSED ? (const u32*)rbase->dev : nullptr, mode == PED_COMMIT_FUSED ? rbase->fp : FbParams{}, mode, ext);
+  if (mode == PED_COMMIT_CHAIN && (rc = fixedbase_launch(c, rbase, n, dr, ext, /*chain=*/1))) return rc;
+  prof_mark(c, 1);
+  if ((rc = normalize_launch(c, n, ext, point ? o.dev : c->ws_tmp[2].p, 0))) return rc;
+  if (!point) hipLaunchKernelGGL(k_affine_u, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (const void*)c->ws_tmp[2].p, o.dev);
+  prof_mark(c, 2);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
 JJ_API int jj_batch_normalize(jj_ctx* c, size_t n, const void* ext160, void* out64) {
   if (!c) return JJ_ERR_INVALID;
   JJ_ENTER(c);

@@ -145,7 +145,7 @@ struct jj_ctx {
   int cus = 0, clock_khz = 0, wave = 64;
   std::string err;
   // staging for host-pointer arguments (inputs 0..3, outputs 0..1) and kernel workspaces
-  DevBuf in[4], out[2], okb, ws_tmp[4], sqrt_tabs;      // (the workspaces of the MSM live in its lanes)
+  DevBuf in[6], out[2], okb, ws_tmp[4], sqrt_tabs;      // (the workspaces of the MSM live in its lanes)
   // kernel workspaces of the batch entry points: extended SoA, normalisation scratch, var-base window tables, the waves' work cursor.
   // Every launch helper goes through `ws`; the host-buffer pipeline points it at the set of the chunk's slot (its two slots run on
   // their own compute streams, so that the kernels of neighbouring chunks overlap), everything else uses ws0.
@@ -293,7 +293,7 @@ struct OutRef { void* user; void* dev; size_t bytes; bool host; };
 // A host array is staged whole in c->in[slot], or written to *buf before it is copied out; the pipeline gives every chunk its own slots.
 struct ArgIn { const void* p; size_t elem; int slot; };
 struct ArgOut { void* p; size_t elem; DevBuf* buf; };
-constexpr int ARGS_IN_MAX = 4, ARGS_OUT_MAX = 2;          // = jj_ctx::in[], the outputs of jj_decompress
+constexpr int ARGS_IN_MAX = 4, ARGS_OUT_MAX = 2;          // = jj_ctx::in[0..3] (in[4], in[5]: jj_pedersen_commit_vartime alone), the outputs of jj_decompress
 static inline SoA soa_of(DevBuf& b, size_t n) { SoA s; s.base = (u32*)b.p; s.n = n; return s; }
 static inline unsigned blocks_for(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 static inline size_t sig_up(size_t x) { return (x + 255) & ~(size_t)255; }          // the regions of the signature workspaces start on 256 bytes

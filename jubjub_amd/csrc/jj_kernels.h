@@ -1352,6 +1352,56 @@ __global__ void __launch_bounds__(256) k_pedersen_scalars(size_t n, const uint8_
   _Pragma("unroll") for (int x = 0; x < 8; x++) { const u64 t = (u64)d[x] + (FR_MODULUS_W[x] & addr) + cy; d[x] = (u32)t; cy = t >> 32; }
   store8(scalars32, (size_t)j * n + i, d);
 }
+// k_pedersen_commit (jj_pedersen_commit_vartime): H(M) + [r] R per unit.  The walk of k_pedersen_gather over a message whose fields lie in up to
+// four row arrays (PedWinSrc names the source of every piece; pos and the clamp dword are formed per source), and then, by `mode`:
+//   PED_COMMIT_HASH   nothing more: the plain multi-source hash
+//   PED_COMMIT_FUSED  the walk of k_fixedbase_gather over R's gathered table (window_bits 8..16) in the SAME accumulator: the recode addition,
+//                     the unsigned top window, then ceil(253 / w) - 1 signed ones.  It is one loop over nwin + W entries, so the first entry of
+//                     the blinding walk is fetched before the message's last addition
+//   PED_COMMIT_CHAIN  all five coordinates are left for the LDS kernel of R's table (fixedbase_launch with chain = 1)
+// One add_signed in the code, no scratch.  VARIABLE-TIME in the message (and, FUSED, in r: both table addresses depend on them).
+enum { PED_COMMIT_HASH = 0, PED_COMMIT_FUSED = 1, PED_COMMIT_CHAIN = 2 };
+__global__ void __launch_bounds__(256) k_pedersen_commit(size_t n, PedSrcs S, const PedWinSrc* __restrict__ plan, int nwin, const u32* __restrict__ table, const void* __restrict__ r32,
+                                                         const u32* __restrict__ rtable, FbParams fp, int mode, SoA ext) {
+  const size_t T = (size_t)gridDim.x * blockDim.x;
+  const int total = nwin + (mode == PED_COMMIT_FUSED ? fp.W : 0);
+  #pragma unroll 1
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += T) {
+    u32 k[8];
+    zero8(k);
+    if (mode == PED_COMMIT_FUSED) {                            // the scalar as k_fixedbase_gather reads it: mod 2^252, plus the recoding constant
+      load8(k, r32, idx);
+      k[7] &= 0x0fffffffu;
+      u64 c = 0;
+      _Pragma("unroll") for (int i = 0; i < 8; i++) { const u64 t = (u64)k[i] + fp.recode[i] + c; k[i] = (u32)t; c = t >> 32; }
+    }
+    // entry `step` of the walk and its sign mask: a window of the message, then R's windows from the top (unsigned) one down
+    auto entry = [&](int step, u32& neg) -> ANiels {
+      if (step < nwin) {
+        const u32 a = Pedersen::index(plan[step], Pedersen::raw_bits_src(S, (u32)idx, plan[step]), neg);
+        return lds_aniels(table + (size_t)a * GNIELS_WORDS);
+      }
+      const int i = fp.W - 1 - (step - nwin);
+      const int d = (int)fb_window(k, fp.w, i) - (i == fp.W - 1 ? 0 : (int)fp.E);
+      neg = d < 0 ? ~0u : 0u;
+      return lds_aniels(rtable + ((size_t)i * (fp.E + 1) + (u32)(d < 0 ? -d : d)) * GNIELS_WORDS);
+    };
+    Ext acc = Curve::identity();
+    if (total > 0) {
+      u32 neg;
+      ANiels e = entry(0, neg);
+      #pragma unroll 1
+      for (int i = 0; i < total; i++) {
+        const ANiels s = e;
+        const u32 smask = neg;
+        if (i + 1 < total) e = entry(i + 1, neg);             // fetch the next entry before this addition
+        acc = Curve::add_signed<true>(acc, s, smask);
+      }
+    }
+    ext.put(0, idx, acc.u); ext.put(1, idx, acc.v); ext.put(2, idx, acc.z);
+    if (mode == PED_COMMIT_CHAIN) { ext.put(3, idx, Fq::carry(acc.t1)); ext.put(4, idx, Fq::carry(acc.t2)); }
+  }
+}
 // the u-coordinates of affine points: the first 32 of every 64 bytes (jj_pedersen_hash_vartime without JJ_PEDERSEN_POINT)
 __global__ void __launch_bounds__(256) k_affine_u(size_t n, const void* aff64, void* out32) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

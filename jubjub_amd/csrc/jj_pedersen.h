@@ -1,6 +1,7 @@
-// Windowed Pedersen hashes (jj_pedersen_table_create, jj_pedersen_hash_vartime, jj_pedersen_scalars): the table layout, the per-window plan of
-// a call and the device functions that turn a unit's row into table indices.  Kernels: k_pedersen_gather and k_pedersen_scalars in jj_kernels.h.
-// Included by jj_kernels.h and, with -DJJ_HOST_EMU, by tests/cpp/emu_pedersen.cpp.
+// Windowed Pedersen hashes (jj_pedersen_table_create, jj_pedersen_hash_vartime, jj_pedersen_scalars, jj_pedersen_commit_vartime): the table
+// layout, the per-window plan of a call and the device functions that turn a unit's row into table indices.  Kernels: k_pedersen_gather,
+// k_pedersen_scalars and k_pedersen_commit in jj_kernels.h.
+// Included by jj_kernels.h and, with -DJJ_HOST_EMU, by tests/cpp/emu_pedersen.cpp and tests/cpp/emu_commit.cpp.
 //
 // The function.  A message M is `prefix_bits` bits of a call constant followed by up to four fields of the unit's row, every bit taken LSB-first
 // within its byte.  M is padded with zero bits to a multiple of 3 and cut into chunks (s0, s1, s2), enc = (1 - 2 s2)(1 + s0 + 2 s1) in +-{1..4};
@@ -25,6 +26,10 @@
 // `byte` of the row; a lane reads the aligned dword of that byte and the next one, joins them with a funnel shift (v_alignbit_b32) and masks.
 // The second load is clamped to the last dword that holds a byte the fields cover in the lane's OWN row: the last row of the caller's array may
 // end in the middle of a dword directly in front of memory that is not the caller's, and no dword beyond that one is ever read.
+//
+// Several sources (jj_pedersen_commit_vartime).  The message's fields may lie in up to four row arrays, each with its own stride; a field is a
+// triple (src, byte_offset, nbits).  The plan of such a call is a PedWinSrc per window: the PedWin of the same message plus the source of every
+// piece.  A lane forms pos and the clamp dword from the source's OWN stride and cover, so the rule above holds for every source separately.
 #pragma once
 #include "jj_blake2b.h"      // Blake2b::funnel
 #include <string.h>
@@ -34,7 +39,7 @@
 namespace jj {
 
 constexpr int PED_DEFAULT_WINDOW = 4;      // what window_chunks = 0 means
-constexpr int PED_MAX_SEG = 8, PED_MAX_CHUNKS = 63, PED_MAX_WINDOW = 4, PED_MAX_FIELDS = 4, PED_MAX_PIECES = 4;
+constexpr int PED_MAX_SEG = 8, PED_MAX_CHUNKS = 63, PED_MAX_WINDOW = 4, PED_MAX_FIELDS = 4, PED_MAX_PIECES = 4, PED_MAX_SRC = 4;
 
 struct PedPiece { u32 byte, shift, mask, dst; };      // bits [shift, shift + popcount(mask)) from byte `byte` of the row, placed at bit `dst` of raw
 struct PedWin {
@@ -48,6 +53,8 @@ struct PedWin {
   PedPiece pc[PED_MAX_PIECES];
 };
 struct PedSegs { int first[PED_MAX_SEG + 1]; };       // segment j owns windows first[j] .. first[j + 1] - 1 of the plan
+struct PedWinSrc : PedWin { u32 src[PED_MAX_PIECES]; };                                   // src[p]: the source that piece p reads
+struct PedSrcs { const uint8_t* rows[PED_MAX_SRC]; u32 stride[PED_MAX_SRC], cover[PED_MAX_SRC]; };      // a call's row arrays (4-byte aligned bases), their strides and covered bytes per row
 
 // ---- layout arithmetic, host and device
 constexpr u32 ped_sub_entries(int t) { return 1u << (3 * t - 1); }
@@ -77,6 +84,21 @@ struct Pedersen {
     return w.entry0 + ((raw & ((1u << w.top) - 1u)) ^ (negmask & w.flip));
   }
   static JJ_DEV u32 last_dword(u32 pos, u32 cover) { return (pos + cover - 1u) & ~3u; }
+  // element s of a four-entry array by compares: s is wave-uniform, and an indexed read of a kernel argument would park the array in scratch
+  template <class T> static JJ_DEV T pick(const T (&a)[PED_MAX_SRC], u32 s) {
+    T r = a[0];
+    _Pragma("unroll") for (u32 q = 1; q < (u32)PED_MAX_SRC; q++) r = s == q ? a[q] : r;
+    return r;
+  }
+  // raw_bits over several sources: pos and the clamp dword of unit `unit` are formed per piece from the piece's own source
+  static JJ_DEV u32 raw_bits_src(const PedSrcs& S, u32 unit, const PedWinSrc& w) {
+    u32 raw = w.konst;
+    for (u32 p = 0; p < w.np; p++) {
+      const u32 s = w.src[p], pos = unit * pick(S.stride, s);
+      raw |= piece(pick(S.rows, s), pos, last_dword(pos, pick(S.cover, s)), w.pc[p]);
+    }
+    return raw;
+  }
 };
 
 // ---- the plan of one call (host).  fields: nfields pairs (byte_offset, nbits), checked by the caller.  Returns the windows the message
@@ -127,6 +149,36 @@ inline std::vector<PedWin> ped_build_plan(int nseg, int c, int w, u32 prefix, in
     segs->first[j + 1] = (int)plan.size();
   }
   for (int j = nseg; j < PED_MAX_SEG; j++) segs->first[j + 1] = (int)plan.size();
+  return plan;
+}
+// The plan of a call over several sources.  fields: nfields triples (src, byte_offset, nbits), checked by the caller.  The windows are those of
+// ped_build_plan over the pairs (byte_offset, nbits); a window's pieces come in field order, one for every field that meets the window's bits,
+// which is how their sources are found again here.  cover[s]: the bytes of a row of source s that its fields cover (0 for an unused source).
+inline std::vector<PedWinSrc> ped_build_plan_src(int nseg, int c, int w, u32 prefix, int prefix_bits, int nfields, const uint32_t* fields, PedSegs* segs, u32 cover[PED_MAX_SRC]) {
+  uint32_t pairs[2 * PED_MAX_FIELDS] = {0};
+  u32 start[PED_MAX_FIELDS + 1];
+  u64 cov[PED_MAX_SRC] = {0, 0, 0, 0};
+  u32 L = (u32)prefix_bits;
+  for (int f = 0; f < nfields; f++) {
+    const u32 s = fields[3 * f], off = fields[3 * f + 1], nb = fields[3 * f + 2];
+    pairs[2 * f] = off; pairs[2 * f + 1] = nb;
+    start[f] = L; L += nb;
+    cov[s] = std::max(cov[s], (u64)off + ((u64)nb + 7u) / 8u);
+  }
+  start[nfields] = L;
+  for (int s = 0; s < PED_MAX_SRC; s++) cover[s] = (u32)cov[s];               // 2^32 travels as 0, as in ped_build_plan
+  u32 one;
+  const std::vector<PedWin> base = ped_build_plan(nseg, c, w, prefix, prefix_bits, nfields, pairs, segs, &one);
+  std::vector<PedWinSrc> plan(base.size());
+  for (size_t k = 0; k < base.size(); k++) {
+    PedWinSrc& x = plan[k];
+    memset(&x, 0, sizeof x);
+    static_cast<PedWin&>(x) = base[k];
+    const u32 b0 = 3u * (x.seg * (u32)c + x.chunk0), b1 = std::min(b0 + 3u * x.t, L);
+    u32 p = 0;
+    for (int f = 0; f < nfields; f++)
+      if (std::max(b0, start[f]) < std::min(b1, start[f + 1])) x.src[p++] = fields[3 * f];
+  }
   return plan;
 }
 

@@ -514,7 +514,7 @@ JJ_API int jj_ctx_destroy(jj_ctx* c) {
   if (!c) return JJ_ERR_INVALID;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  DevBuf* all[] = {&c->in[0], &c->in[1], &c->in[2], &c->in[3], &c->out[0], &c->out[1], &c->okb, &c->ws0.ext, &c->ws0.scratch, &c->ws0.tables,
+  DevBuf* all[] = {&c->in[0], &c->in[1], &c->in[2], &c->in[3], &c->in[4], &c->in[5], &c->out[0], &c->out[1], &c->okb, &c->ws0.ext, &c->ws0.scratch, &c->ws0.tables,
                    &c->ws_tmp[0], &c->ws_tmp[1], &c->ws_tmp[2], &c->ws_tmp[3], &c->sqrt_tabs, &c->ws0.cursor,
                    &c->pipe.wset.ext, &c->pipe.wset.scratch, &c->pipe.wset.tables, &c->pipe.wset.cursor, &c->sigseg, &c->sigseg_out, &c->sigeach, &c->ka, &c->b2s};
   for (jj_msm_job* j : c->job_pool) { if (j->host) (void)hipHostFree(j->host); if (j->gdev) (void)hipFree(j->gdev); (void)hipEventDestroy(j->ev); delete j; }

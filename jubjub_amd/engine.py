@@ -27,6 +27,8 @@ FLAG_KA_HASH_INPUT = 64        # jj_ka_kdf only: hash share || encoding
 KA_SAPLING_FLAGS = FLAG_ZIP216 | FLAG_KA_COFACTOR | FLAG_KA_HASH_INPUT      # the Sapling recipient's ka_kdf flags
 SAPLING_GD_PERSONAL = b"Zcash_gd"                # the personalisation of Sapling's diversified base g_d: a documented example of group_hash's `personal` (the C library does not contain it)
 SAPLING_PH_PERSONAL = b"Zcash_PH"                # the personalisation of Sapling's Pedersen-hash generators: the other example (the protocol's prefix, its URS, is the caller's to supply)
+SAPLING_EXPAND_PERSONAL = b"Zcash_ExpandSeed"    # the personalisation of Sapling's PRF^expand: the documented example of note_check's `expand_personal` (the C library does not contain it)
+SAPLING_NOTE_PREFIX, SAPLING_NOTE_PREFIX_BITS = 0b111111, 6      # the six one bits in front of a note commitment's message (note_commit)
 GROUP_HASH_FLAGS = FLAG_ZIP216 | FLAG_NOT_SMALL_ORDER | FLAG_CLEAR_COFACTOR  # the group hash of the Zcash specification: decode, refuse small order, multiply by 8
 
 
@@ -856,6 +858,124 @@ class Engine:
             layers.append(cur)
             layer += 1
         return layers
+
+    def pedersen_commit(self, ped, rtab, sources, fields, r, prefix=0, prefix_bits=0, point=False, out=None):
+        """Windowed Pedersen commitments H(M_i) + [r_i] R in one call (jj_pedersen_commit_vartime).  H is pedersen_hash over `ped`; R is the
+        base of `rtab`, a fixedbase_table of any window_bits; r is (n, 32) raw bytes read as fixedbase_mul reads its scalars.  Message i is
+        prefix_bits bits of `prefix`, then the fields in the order given: `sources` is a list of up to four (n, L_s) uint8 arrays -- numpy
+        arrays, or CUDA tensors of one kind; a view whose rows lie a fixed number of bytes apart is read where it is, as group_hash reads
+        one -- and `fields` up to four (src, byte_offset, nbits) triples.  rtab = None with r = None is the plain multi-source hash.
+        -> (n, 32) canonical u-coordinates, or (n, 64) affine points with point=True, of the sources' kind, or `out`.
+        VARIABLE-TIME in the message (the decoder of the fields and the table addresses).  The blinding term is CONSTANT-TIME in r with an
+        LDS rtab (window_bits 0, 6, 7) and variable-time with a gathered one (8..16)."""
+        if (rtab is None) != (r is None):
+            raise ValueError("rtab and r: both or neither (the hash-only form)")
+        srcs = [_Rows(s, "sources[%d]" % k) for k, s in enumerate(sources)]
+        if len(srcs) > 4:
+            raise ValueError("sources: at most four arrays")
+        flat = [tuple(int(v) for v in f) for f in fields]
+        if len(flat) > 4 or any(len(f) != 3 or min(f) < 0 or max(f) >= 1 << 32 for f in flat):
+            raise ValueError("fields: up to four (src, byte_offset, nbits) triples of 32-bit values expected")
+        for s, off, nb in flat:
+            if s >= len(srcs) or nb < 1 or off + (nb + 7) // 8 > srcs[s].len:
+                raise ValueError("field (%d, %d, %d): no such source, empty, or past the %s bytes of its rows" % (s, off, nb, srcs[s].len if s < len(srcs) else "-"))
+        ra = None if r is None else _Arg(r, 32)
+        if not srcs and ra is None:
+            raise ValueError("sources or r: something must say how many units there are")
+        n = srcs[0].n if srcs else ra.n
+        if any(s.n != n for s in srcs) or (ra is not None and ra.n != n):
+            raise ValueError("length mismatch: %d units expected in every source and in r" % n)
+        if any(s.torch != srcs[0].torch for s in srcs):
+            raise ValueError("sources: numpy arrays or CUDA tensors, of one kind")
+        like = srcs[0] if srcs else ra
+        width = 64 if point else 32
+        if out is None:
+            out, optr = self._alloc(like, n, width)
+        else:
+            oa = _Arg(out, width)
+            if oa.n != n or oa.torch != like.torch or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x %d bytes of the sources' kind expected" % (n, width))
+            optr = oa.ptr
+        self._bind_stream(srcs + ([ra] if ra is not None else []))
+        cs = (C.c_void_p * 4)(*[s.ptr for s in srcs])
+        cst = (C.c_size_t * 4)(*[s.stride for s in srcs])
+        cf = (C.c_uint32 * 12)(*[v for f in flat for v in f])
+        self._check(self._lib.jj_pedersen_commit_vartime(self._ctx, ped._h, rtab._h if rtab is not None else None, C.c_size_t(n), C.c_uint(int(prefix) & 0xFFFFFFFF),
+                                                          C.c_int(int(prefix_bits)), C.c_int(len(srcs)), cs, cst, C.c_int(len(flat)), cf, ra.ptr if ra is not None else None,
+                                                          C.c_uint(FLAG_PEDERSEN_POINT if point else 0), optr))
+        return out
+
+    def note_commit(self, ped, rtab, value_rows, value_offset, gd32, pkd32, rcm32):
+        """The u-coordinate of a note commitment -> cm_u (n, 32): pedersen_commit over the prefix 0b111111 (6 bits), the 64 value bits at
+        byte value_offset of value_rows, repr(g_d) and repr(pk_d) (256 bits each), blinded by rcm32 over rtab's base.  582 bits, 194 chunks:
+        `ped` is the caller's four-segment table of 63 chunks (the last segment holds 5).  The generators are the caller's: the library
+        knows no protocol.  Variable-time in the note's contents; rcm is constant-time with an LDS rtab."""
+        return self.pedersen_commit(ped, rtab, [value_rows, gd32, pkd32], ((0, int(value_offset), 64), (1, 0, 256), (2, 0, 256)), rcm32,
+                                    prefix=SAPLING_NOTE_PREFIX, prefix_bits=SAPLING_NOTE_PREFIX_BITS)
+
+    def note_check(self, ivk32, plaintexts, cmu, ped, rtab, gd_personal, gd_prefix, expand_personal, epk=None, leads=(2,)):
+        """The check that follows a trial-decryption hit -> verdict (n,) uint8, the codes of sigverify_each: 1 the row is a note, 0 the
+        commitment or epk differs, 2 malformed (a lead byte not in `leads`, a diversifier with no point, or for lead 1 an rseed that is not a
+        canonical Fr).  plaintexts: (n, L >= 52) rows as ka_open_aead returns them -- lead = row[0], d = row[1:12], v = row[12:20], rseed =
+        row[20:52]; cmu, epk: (n, 32); ivk32: 32 bytes.  Steps, all on the arrays' device (nothing visits the host with CUDA tensors):
+        g_d = group_hash(d, gd_personal, gd_prefix); pk_d = varbase_mul(ivk, g_d), the CONSTANT-TIME ladder; both compressed; lead 2:
+        rcm = sig_challenge(None, None, rseed || 0x04, expand_personal) and, with epk given, esk likewise with 0x05 and
+        varbase_mul_compressed(esk, g_d) == epk; lead 1: rcm = rseed, no epk check; note_commit(..) == cmu.
+        SAPLING_GD_PERSONAL and SAPLING_EXPAND_PERSONAL are the documented examples; ped, rtab and gd_prefix are the caller's.
+        VARIABLE-TIME in the note's contents (the decoder of the group hash, the Pedersen table addresses); CONSTANT-TIME in ivk and esk,
+        and in rcm with an LDS rtab.  Real hits are rare: this serves rescans and callers who check every output they created."""
+        shape = tuple(plaintexts.shape) if hasattr(plaintexts, "shape") else None
+        if shape is None or len(shape) != 2 or shape[1] < 52:
+            raise ValueError("plaintexts: shape (n, L) with L >= 52 expected, got %r" % (shape,))
+        n, on_dev = shape[0], _is_torch(plaintexts)
+        if on_dev:
+            import torch as xp
+
+            def like(x):
+                return x if _is_torch(x) else xp.from_numpy(_host_bytes(x)).to(plaintexts.device)
+
+            def cat(a, b):
+                return xp.cat([a, b], dim=1)
+
+            def every(m):
+                return m.all(dim=1)
+
+            rows, u8 = plaintexts, xp.uint8
+            const = lambda v: xp.full((n, 1), v, dtype=xp.uint8, device=rows.device)      # noqa: E731
+        else:
+            xp = np
+
+            def like(x):
+                return x.cpu().numpy() if _is_torch(x) else _host_bytes(x)
+
+            def cat(a, b):
+                return np.concatenate([a, b], axis=1)
+
+            def every(m):
+                return m.all(axis=1)
+
+            rows, u8 = _host_bytes(plaintexts).reshape(shape), np.uint8
+            const = lambda v: np.full((n, 1), v, np.uint8)      # noqa: E731
+        cmu, ivk = like(cmu).reshape(n, 32), like(ivk32).reshape(1, 32)
+        lead, rseed = rows[:, 0], rows[:, 20:52]
+        gd, gd_ok = self.group_hash(rows[:, 1:12], gd_personal, gd_prefix)
+        gd[:, 32] |= 1 - gd_ok                                  # a row without a point carries (0, 0): the identity (0, 1) goes through the ladders instead
+        ivk_n = ivk.repeat(n, 1) if on_dev else np.repeat(ivk, n, axis=0)
+        gd32, pkd32 = self.compress(gd), self.compress(self.varbase_mul(ivk_n, gd))
+        rcm = self.sig_challenge(None, None, cat(rseed, const(4)), expand_personal)
+        is1 = lead == 1
+        _, fr_ok = self.field_unary_ok("fr", "from_bytes", rseed)
+        rcm = xp.where(is1[:, None], rseed, rcm)
+        good = every(self.note_commit(ped, rtab, rows, 12, gd32, pkd32, rcm) == cmu)
+        if epk is not None:
+            esk = self.sig_challenge(None, None, cat(rseed, const(5)), expand_personal)
+            good = good & (is1 | every(self.varbase_mul_compressed(esk, gd) == like(epk).reshape(n, 32)))
+        known = lead != lead
+        for v in leads:
+            known = known | (lead == int(v))
+        malformed = ~known | (gd_ok == 0) | (is1 & (fr_ok.reshape(n) == 0))
+        good, bad = (good.to(u8), malformed.to(u8)) if on_dev else (good.astype(u8), malformed.astype(u8))
+        return good * (1 - bad) + SIG_MALFORMED * bad              # arithmetic on bytes: no masked store, so no wait for the device
 
     def msm(self, scalars, points):
         return self._sum_like("jj_msm", [scalars, points], [32, 64])

@@ -423,6 +423,21 @@ impl<'a> PedersenTable<'a> {
         assert_eq!(unsafe { jj_pedersen_scalars(self.gpu.0, self.nseg, self.seg_chunks, n, prefix, prefix_bits, rows.as_ptr() as _, row_stride, fields.len() as c_int, fields.as_ptr() as *const u32, out.as_mut_ptr() as _) }, 0);
         out
     }
+    /// `H(M) + [r] R` per unit (`jj_pedersen_commit_vartime`): the message's `fields` (src, byte_offset, nbits) lie in up to four row arrays,
+    /// `sources[s]` holding n rows of `strides[s]` bytes; R is the base of `rbase`, `r` one 32-byte scalar per unit (n = r.len()).  `rbase` None
+    /// with an empty `r`: the plain multi-source hash of `n` units.  -> canonical u-coordinates.  VARIABLE-TIME in the message; r is
+    /// constant-time with an LDS table (`FixedBase`'s default).
+    pub fn commit(&self, rbase: Option<&FixedBase>, sources: &[&[u8]], strides: &[usize], fields: &[[u32; 3]], r: &[[u8; 32]], n: usize, prefix: u32, prefix_bits: c_int) -> Vec<[u8; 32]> {
+        let n = if rbase.is_some() { r.len() } else { n };
+        assert!(sources.len() == strides.len() && sources.len() <= 4 && (rbase.is_some() || r.is_empty()));
+        assert!(sources.iter().zip(strides).all(|(s, st)| s.len() >= n * st));
+        let ptrs: Vec<*const c_void> = sources.iter().map(|s| s.as_ptr() as *const c_void).collect();
+        let mut out = vec![[0u8; 32]; n];
+        let (tab, rp) = match rbase { Some(b) => (b.t as *const JjTable, r.as_ptr() as *const c_void), None => (std::ptr::null(), std::ptr::null()) };
+        assert_eq!(unsafe { jj_pedersen_commit_vartime(self.gpu.0, self.t, tab, n, prefix, prefix_bits, sources.len() as c_int, ptrs.as_ptr(), strides.as_ptr(), fields.len() as c_int,
+                                                       fields.as_ptr() as *const u32, rp, 0, out.as_mut_ptr() as _) }, 0);
+        out
+    }
 }
 impl Drop for PedersenTable<'_> { fn drop(&mut self) { unsafe { jj_fixedbase_table_destroy(self.gpu.0, self.t); } } }
 
