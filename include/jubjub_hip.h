@@ -697,7 +697,7 @@ int jj_sig_challenge(jj_ctx*, size_t n, const void* personal16, const void* r32,
  * k_varbase_mont -- ONE unit per lane for every n: there is no quad-of-lanes form, as with jj_varbase_mul2_vartime, so a call of a few units
  * pays the latency of a full ladder --; the shared normaliser writing to_bytes of the share; k_ka_kdf<hash_input>, one unit per lane.
  * k_varbase_mont, its launch and its code are untouched.
- * OUT OF SCOPE: per-unit scalars (the sender's side: jj_varbase_mul_compressed and a hash of the caller's), the note-commitment
+ * OUT OF SCOPE: per-unit scalars (the sender's side: they are jj_ka_kdf_each's, behind jj_group_hash below), the note-commitment
  * check that follows a hit, and a _vartime variant.  (Poly1305 and the tag check that decides a hit: jj_aead_open, below.)
  *
  * jj_chacha20_xor: out[i][j] = in[i * in_stride + j] xor byte j of the ChaCha20 keystream (RFC 8439 section 2.3/2.4: 32-bit block counter,
@@ -768,8 +768,8 @@ int jj_chacha20_xor(jj_ctx*, size_t n, const void* keys32, const void* nonce12, 
  * through ctypes -- takes 1675.9 ms with 16 processes and 2995.5 ms in one thread per 2^20 rows, 90.2 ms per 2^16 and 3.2 ms per 2^10: nothing is
  * BEHIND.  Bytes moved per row over the time: 1521 GB/s for jj_aead_open at 2^20, about a quarter of the 6 TB/s of HBM; the row-per-lane strided
  * reads look like the limit rather than the arithmetic, which is a supposition from that rate (no counters were read).
- * OUT OF SCOPE: per-unit scalars on the sender's side, the note-commitment check that follows a hit, per-row nonces or aad, and a len that is
- * not a multiple of 4. */
+ * OUT OF SCOPE: per-unit scalars on the sender's side (jj_ka_kdf_each and jj_blake2b make the keys this call opens and seals with), the
+ * note-commitment check that follows a hit, per-row nonces or aad, and a len that is not a multiple of 4. */
 int jj_poly1305(jj_ctx*, size_t n, const void* keys32, const void* in, size_t len, size_t in_stride, void* tag16);
 int jj_aead_open(jj_ctx*, size_t n, const void* keys32, const void* nonce12, const void* aad, size_t aad_len, const void* in, size_t len, size_t in_stride, void* out,
                  uint8_t* ok);
@@ -816,6 +816,70 @@ int jj_aead_seal(jj_ctx*, size_t n, const void* keys32, const void* nonce12, con
 int jj_blake2s(jj_ctx*, size_t n, const void* personal8, const void* prefix, size_t prefix_len, const void* msgs, size_t msg_len, size_t msg_stride, void* out32);
 int jj_group_hash(jj_ctx*, size_t n, const void* personal8, const void* prefix, size_t prefix_len, const void* msgs, size_t msg_len, size_t msg_stride, unsigned flags,
                   void* out64, uint8_t* ok);
+
+/* ---- the sender's side of a note: raw BLAKE2b digests over rows gathered from several arrays, and the key agreement with one secret scalar
+ * PER ROW.  With them the ciphertexts of n outputs can be created, and sent notes recovered with an outgoing viewing key, without a key or
+ * a share visiting the host.  The library still knows no protocol: personalisations, decoding flags and layouts remain the caller's.
+ *
+ * jj_blake2b: out[i] = BLAKE2b-digest_len(personal16; prefix || S_0[i] || .. || S_{nsrc-1}[i]), S_s[i] the lens[s] bytes at
+ * srcs[s] + i * strides[s].  BLAKE2b as in RFC 7693: unkeyed, zero salt, parameter word 0x01010000 | digest_len -- BLAKE2b-256 is its own
+ * hash, not BLAKE2b-512 cut short --, the 16 bytes of personalisation in h[6] and h[7].  out is n x digest_len, dense.
+ *   digest_len  32 or 64; any other value is refused
+ *   personal16  16 bytes in HOST memory, read before the call returns; NULL = sixteen zero bytes
+ *   prefix      prefix_len bytes in HOST memory, read before the call returns; prefix_len 0..4096 and a multiple of 4; NULL only with length 0
+ *   nsrc        0..4; with 0 every row gets the digest of the prefix alone
+ *   srcs, lens, strides   HOST arrays of nsrc entries.  lens[s] a multiple of 4 in 4..65536; strides[s] a multiple of 4, >= lens[s], and
+ *               n * strides[s] <= 2^32;  n <= 2^24.  One array may serve several sources
+ * The sources and out may be host or device pointers, mixed freely; device pointers are 16-byte aligned.  A host source is staged as exactly
+ * the (n - 1) * stride + len bytes that are read.  out must not overlap a source: that is checked and refused.
+ * Every violation returns JJ_ERR_INVALID before anything is staged or launched, with out untouched: a NULL context, a NULL out or source with
+ * n > 0, a misaligned device pointer, and srcs, lens, strides, prefix or personal16 in device memory among them.  n = 0 succeeds and touches
+ * nothing.  The lock and stream rules are those of jj_ka_kdf: NOTHING has to happen between this call writing a device out and jj_aead_open or
+ * jj_aead_seal reading it as keys32.
+ * TIMING: nothing in the instruction stream or in any address depends on the data -- the prefix may be a viewing key --; the block loop runs by
+ * the lengths, which are the same in every lane.
+ * Kernel k_blake2b<32|64> (jj_blake2b.h: Blake2bRows on top of the compression and the rotations of k_sig_challenge's Blake2bT, reused as they
+ * are), one row per lane, ONE launch.  The whole blocks of the prefix are compressed ONCE on the host, never a block that could be the final
+ * one; the kernel gets the midstate, t, the prefix's tail and a per-call piece plan (which source, which byte offset, how many dwords) as
+ * arguments.  Every length is the same in every lane, so the block loop, the piece boundaries and the final-block flag are uniform; every
+ * index into m[] is a compile-time constant (no scratch); rows are read as aligned dwords, never outside a lane's own lens[s] bytes, and the
+ * row offsets are formed in 64 bits.  tests/test_codegen_ovk.py pins on the gfx950 assembly: no scratch, at most 128 VGPRs, v_alignbit_b32
+ * rotations, no sub-dword load.
+ * The ock shape of Sapling: digest_len 32, prefix = the 32 bytes of ovk, three sources of 32 bytes (cv, cmu, epk): one compression per row.
+ *
+ * jj_ka_kdf_each: exactly jj_ka_kdf, with these differences:
+ *   sk32   n x 32, host or device: each row is read as jj_varbase_mul reads a scalar, the low 252 bits, an integer never reduced mod r
+ *   h32    with JJ_KA_HASH_INPUT the second hashed part is h32[i] (n x 32) when h32 is not NULL and p32[i] when it is NULL: the sender hashes
+ *          share_i || epk_i, and epk_i is not the point that was multiplied (that is pk_d_i).  A non-NULL h32 without that flag: JJ_ERR_INVALID
+ * The decoder bits, JJ_KA_COFACTOR, the ok and zero-key rule, the chunks of 2^20 units, the pointer rules and the refusals (JJ_ERR_INVALID before
+ * any device work, the outputs untouched; n = 0 succeeds and touches nothing) are jj_ka_kdf's.
+ * CONSTANT-TIME in the scalars and in the shares, on the same grounds as jj_ka_kdf: the ladder and the recovery are the functions of
+ * k_varbase_mont called as they are, the scalars are loaded per lane as k_varbase_mont loads them, and tests/test_codegen_ovk.py holds the
+ * loop of the new kernel to k_varbase_mont's counts of conditional branches, v_bfi_b32 and v_mad_i64_i32 per bit, with no v_cndmask, no scalar
+ * select, no memory access and no call in it, no scratch, at most 168 VGPRs.  A host sk32 passes through a staging slot of the context on the
+ * device; those n x 32 bytes are cleared on the launch stream behind the last chunk, as jj_ka_kdf clears its one scalar.  (An array of 1 MB and
+ * more also passes through the context's page-locked HOST slots, which are host memory like the caller's own array and are not cleared.)
+ * Kernels, per chunk: jj_ka_kdf's, with k_varbase_mont_ka_each<cofactor> in the place of k_varbase_mont_ka; k_ka_kdf<true> is launched with
+ * h32 in the place of p32.  k_varbase_mont, k_varbase_mont_ka, k_varbase_mont_x1, k_ka_kdf and their launches are untouched.
+ * OUT OF SCOPE: compaction of hit rows through the C ABI (Engine.ovk_open gathers them with index operations of numpy or torch), a
+ * quad-of-lanes form for small n, ragged lengths, keyed or salted BLAKE2b, digest lengths other than 32 and 64, per-row nonces, and a
+ * jj_multi_* form.
+ * Measured on an MI355X (profiles/ovk_ab.txt, tools/ovk_ab.py: device-resident inputs and results, three alternating rounds of one process per
+ * route, median; host-clock time per call over a window of back-to-back calls, so a figure below the launch latency is throughput, not the
+ * latency of one call; the expectation stands in the file above the numbers, written before the run).  jj_blake2b at the ock shape: 0.099 ms
+ * per 2^20 rows (10.6 G rows/s) -- the expectation was the 0.084 ms of the traced one-block k_sig_challenge: one compression, four times the
+ * loads --, 0.015 ms at 2^16 and at 2^10; with jj_aead_open at len 64 in a stride of 80 behind it, the per-output cost of an ovk rescan,
+ * 0.202 ms per 2^20 (5.2 G outputs/s), 0.028 ms at 2^16 and 2^10; hashlib over the same 128-byte rows: 318 ms per 2^20 in one thread, 213 ms
+ * in 16 processes.  jj_ka_kdf_each: 14.293 ms per 2^20 rows [14.291 .. 14.308] against 14.507 ms for the composed five-call route on the same
+ * build (jj_decompress, jj_varbase_mul, jj_point_mul_by_cofactor, jj_compress, jj_blake2b) and 14.411 ms for the parent commit's four-call
+ * route without any hash: AHEAD of both by more than the larger range; 2^16: 1.640 against 1.716 and 1.700 ms, AHEAD.  BEHIND at 2^10: 1.208 ms
+ * against 0.752 and 0.744 ms -- jj_varbase_mul has a quad-of-lanes ladder up to vb_quad_max units and this call has none, as expected. */
+int jj_blake2b(jj_ctx*, size_t n, int digest_len, const void* personal16,
+               const void* prefix, size_t prefix_len,
+               int nsrc, const void* const* srcs, const size_t* lens, const size_t* strides,
+               void* out);
+int jj_ka_kdf_each(jj_ctx*, size_t n, const void* sk32, const void* p32, const void* h32,
+                   unsigned flags, const void* personal16, void* key32, uint8_t* ok);
 
 /* ---- windowed Pedersen hashes: one launch for n units, every segment in one accumulator.  VARIABLE-TIME (public inputs): the table address
  * depends on the message; a caller with secret inputs composes jj_pedersen_scalars with jj_fixedbase_multi_mul on the LDS tables.

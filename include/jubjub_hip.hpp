@@ -570,6 +570,29 @@ inline KaKeys ka_kdf(const Context& c, const Bytes32& sk, const std::vector<Byte
   c.check(jj_ka_kdf(c.raw(), P.size(), sk.data(), P.data(), flags, personal ? personal->data() : nullptr, r.keys.data(), r.ok.data()));
   return r;
 }
+// The same with one secret scalar PER ROW (jj_ka_kdf_each: the sender's side of a note): sk[i] is read as jj_varbase_mul reads a scalar; with
+// JJ_KA_HASH_INPUT the second hashed part is (*hash_input)[i] when hash_input is given and P[i] when it is nullptr.  CONSTANT-TIME in the
+// scalars and in the shares.
+inline KaKeys ka_kdf_each(const Context& c, const std::vector<Bytes32>& sk, const std::vector<Bytes32>& P, unsigned flags, const std::vector<Bytes32>* hash_input = nullptr,
+                          const std::array<uint8_t, 16>* personal = nullptr) {
+  if (sk.size() != P.size() || (hash_input && hash_input->size() != P.size())) throw Error(JJ_ERR_INVALID, "length mismatch");
+  KaKeys r{std::vector<Bytes32>(P.size()), std::vector<uint8_t>(P.size())};
+  c.check(jj_ka_kdf_each(c.raw(), P.size(), sk.data(), P.data(), hash_input ? hash_input->data() : nullptr, flags, personal ? personal->data() : nullptr, r.keys.data(), r.ok.data()));
+  return r;
+}
+// Raw BLAKE2b digests over rows gathered from up to four arrays (jj_blake2b): out[i] = BLAKE2b-digest_len(personal; prefix || S_0[i] || ..),
+// S_s[i] the lens[s] bytes at sources[s] + i * strides[s]; digest_len 32 or 64; lengths, strides and the prefix's length multiples of 4.
+// The result is n x digest_len bytes, dense.  personal == nullptr is sixteen zero bytes.  The library knows no protocol: personalisation,
+// prefix and layout are the caller's (Sapling's ock: digest_len 32, prefix = ovk, the sources cv, cmu, epk).
+inline std::vector<uint8_t> blake2b(const Context& c, size_t n, int digest_len, const std::vector<const uint8_t*>& sources, const std::vector<size_t>& lens,
+                                    const std::vector<size_t>& strides, const std::vector<uint8_t>& prefix = {}, const std::array<uint8_t, 16>* personal = nullptr) {
+  if (sources.size() != lens.size() || sources.size() != strides.size() || sources.size() > 4 || (digest_len != 32 && digest_len != 64)) throw Error(JJ_ERR_INVALID, "length mismatch");
+  std::vector<const void*> ptrs(sources.begin(), sources.end());
+  std::vector<uint8_t> out(n * (size_t)digest_len);
+  c.check(jj_blake2b(c.raw(), n, digest_len, personal ? personal->data() : nullptr, prefix.empty() ? nullptr : prefix.data(), prefix.size(), (int)sources.size(),
+                     ptrs.empty() ? nullptr : ptrs.data(), lens.empty() ? nullptr : lens.data(), strides.empty() ? nullptr : strides.data(), out.data()));
+  return out;
+}
 // One RFC 8439 ChaCha20 key per row (jj_chacha20_xor): rows of `len` bytes at a stride of in_stride in `in`, a dense n x len result; len and
 // in_stride multiples of 4, len in 4..1024; nonce == nullptr is twelve zero bytes.
 inline std::vector<uint8_t> chacha20_xor(const Context& c, const std::vector<Bytes32>& keys, const std::vector<uint8_t>& in, size_t len, size_t in_stride, uint32_t counter = 0,

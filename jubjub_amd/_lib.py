@@ -60,6 +60,8 @@ _SIGS.update({
     "jj_sigverify_each": [_vp, _sz, _vp, _vp, _vp, _vp, C.c_uint, _vp],
     "jj_sig_challenge": [_sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
     "jj_ka_kdf": [_sz, _vp, _vp, C.c_uint, _vp, _vp, _u8p],
+    "jj_ka_kdf_each": [_sz, _vp, _vp, _vp, C.c_uint, _vp, _vp, _u8p],
+    "jj_blake2b": [_sz, C.c_int, _vp, _vp, _sz, C.c_int, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz), _vp],
     "jj_chacha20_xor": [_sz, _vp, _vp, C.c_uint, _vp, _sz, _sz, _vp],
     "jj_poly1305": [_sz, _vp, _vp, _sz, _sz, _vp],
     "jj_aead_open": [_sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _u8p],

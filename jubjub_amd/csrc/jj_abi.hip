@@ -843,6 +843,105 @@ JJ_API int jj_ka_kdf(jj_ctx* c, size_t n, const void* sk32, const void* p32, uns
     return JJ_OK;
   });
 }
+// ---- the same with one secret scalar PER ROW (the sender's side of a note: esk_i against pk_d_i, hashed with epk_i): jj_ka_kdf's checks, chunks
+// and workspace (c->ka behind the 256 bytes of jj_ka_kdf's scalar, which this call leaves alone), with k_varbase_mont_ka_each in the place of
+// k_varbase_mont_ka and, under JJ_KA_HASH_INPUT, h32 in the place of p32 as the second hashed part when it is given.  The scalars go through
+// the staging front end like the points; where that staged a host sk32 (c->in[1]) its n x 32 bytes are cleared behind the last chunk.
+static int ka_each_chunk(jj_ctx* c, size_t n, const void* dsk, const void* dp, const void* dh, unsigned flags, const uint64_t (&personal)[2], void* dkey, uint8_t* dok) {
+  int rc;
+  uint8_t* const pts = (uint8_t*)c->ka.p + 256; uint8_t* const enc = pts + sig_up(64 * n);
+  if ((rc = decompress_dev(c, n, dp, flags & KA_DECODER_FLAGS, pts, dok, false))) return rc;
+  if ((rc = ensure_ext(c, n, 3))) return rc;
+  SoA ext = soa_of(c->ws->ext, n);
+  mont_x1_launch(c, n, pts, ext);
+  if (flags & JJ_KA_COFACTOR) hipLaunchKernelGGL(k_varbase_mont_ka_each<true>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dsk, (const void*)pts, ext);
+  else hipLaunchKernelGGL(k_varbase_mont_ka_each<false>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, dsk, (const void*)pts, ext);
+  if ((rc = normalize_launch(c, n, ext, enc, 1))) return rc;
+  if (flags & JJ_KA_HASH_INPUT) hipLaunchKernelGGL(k_ka_kdf<true>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)personal[0], (u64)personal[1], (const void*)enc, dh ? dh : dp, (const uint8_t*)dok, dkey);
+  else hipLaunchKernelGGL(k_ka_kdf<false>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, (u64)personal[0], (u64)personal[1], (const void*)enc, dp, (const uint8_t*)dok, dkey);
+  return JJ_OK;
+}
+JJ_API int jj_ka_kdf_each(jj_ctx* c, size_t n, const void* sk32, const void* p32, const void* h32, unsigned flags, const void* personal16, void* key32, uint8_t* ok) {
+  if (!c) return JJ_ERR_INVALID;
+  if (flags & ~(KA_DECODER_FLAGS | JJ_KA_COFACTOR | JJ_KA_HASH_INPUT)) return JJ_ERR_INVALID;
+  if (h32 && !(flags & JJ_KA_HASH_INPUT)) return JJ_ERR_INVALID;
+  if (n == 0) return JJ_OK;
+  if (!sk32 || !p32 || !key32 || !ok) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  for (const void* p : {sk32, p32, h32, (const void*)key32, (const void*)ok})
+    if (p && ((uintptr_t)p & 15u) && is_device_ptr(p)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  uint64_t personal[2] = {0, 0};
+  if (personal16) memcpy(personal, personal16, 16);
+  const bool sk_staged = !is_device_ptr(sk32);
+  return run_batch(c, n, {{p32, 32, 0}, {sk32, 32, 1}, {h32, h32 ? (size_t)32 : (size_t)0, 2}}, {{key32, 32, &c->out[0]}, {ok, 1, &c->okb}}, 0, 0,
+                   [&](size_t n, const void* const* din, void* const* dout, bool) -> int {
+    const size_t ch = std::min(n, KA_CHUNK);
+    int rc = ensure(c, c->ka, 256 + sig_up(64 * ch) + 32 * ch); if (rc) return rc;
+    rc = for_chunks(n, KA_CHUNK, [&](size_t lo, size_t cn) -> int {
+      return ka_each_chunk(c, cn, (const uint8_t*)din[1] + 32 * lo, (const uint8_t*)din[0] + 32 * lo, din[2] ? (const uint8_t*)din[2] + 32 * lo : nullptr, flags, personal,
+                           (uint8_t*)dout[0] + 32 * lo, (uint8_t*)dout[1] + lo);
+    });
+    if (sk_staged) HIPCHK(c, hipMemsetAsync(c->in[1].p, 0, 32 * n, c->stream));      // (also behind a chunk that failed to queue)
+    return rc;
+  });
+}
+// ---- raw BLAKE2b digests over rows gathered from up to four arrays (kernel: k_blake2b<32|64> in jj_kernels.h; Blake2bRows in jj_blake2b.h):
+// out[i] = BLAKE2b-digest_len(personal16; prefix || S_0[i] || .. || S_{nsrc-1}[i]).  Every argument is checked before anything is staged or
+// launched.  The host compresses the whole blocks of the prefix once (never a block that could be the final one); the kernel gets the
+// midstate, t, the prefix's tail, the piece plan (one piece per source) and the sources' bases and strides as arguments.  The sources go
+// through the staging front end (c->in[0..3]: a device pointer passes through, a host source is copied as the (n - 1) * stride + len bytes
+// that are read) and ONE launch over all n rows follows on the launch stream, no workspace.  A device `out` is written in launch-stream
+// order, where jj_aead_open and jj_aead_seal read their keys32: nothing has to happen between the calls.  The library holds no
+// personalisation and no prefix of any protocol.
+constexpr size_t B2B_PREFIX_MAX = 4096, B2B_LEN_MAX = 65536;
+template <int DIGEST>
+static void b2b_launch(jj_ctx* c, size_t n, const void* personal16, const void* prefix, size_t prefix_len, int nsrc, const size_t* lens, size_t rest, const B2bSrcs& S, void* dout) {
+  B2bMid mid; B2bPlan plan;
+  Blake2bRows<DIGEST>::midstate(mid, (const uint8_t*)personal16, (const uint8_t*)prefix, prefix_len, rest);
+  Blake2bRows<DIGEST>::plan_sources(plan, nsrc, lens);
+  hipLaunchKernelGGL(k_blake2b<DIGEST>, dim3(blocks_for(n)), dim3(256), 0, c->stream, n, mid, plan, S, dout);
+}
+JJ_API int jj_blake2b(jj_ctx* c, size_t n, int digest_len, const void* personal16, const void* prefix, size_t prefix_len, int nsrc, const void* const* srcs, const size_t* lens,
+                      const size_t* strides, void* out) {
+  if (!c) return JJ_ERR_INVALID;
+  if (digest_len != 32 && digest_len != 64) return JJ_ERR_INVALID;
+  if (prefix_len > B2B_PREFIX_MAX || (prefix_len & 3u) || (prefix_len && !prefix)) return JJ_ERR_INVALID;
+  if (nsrc < 0 || nsrc > B2B_MAX_PIECES || (nsrc && (!srcs || !lens || !strides)) || n > ((size_t)1 << 24)) return JJ_ERR_INVALID;
+  JJ_ENTER(c);
+  if ((nsrc && (is_device_ptr(srcs) || is_device_ptr(lens) || is_device_ptr(strides))) || is_device_ptr(prefix) || is_device_ptr(personal16)) {
+    c->err = "jj_blake2b: personal16, prefix, srcs, lens and strides must be in host memory"; return JJ_ERR_INVALID;
+  }
+  size_t rest = 0;
+  for (int s = 0; s < nsrc; s++) {
+    if (lens[s] < 4 || lens[s] > B2B_LEN_MAX || (lens[s] & 3u) || (strides[s] & 3u) || strides[s] < lens[s]) { c->err = "jj_blake2b: a length or stride that is not allowed"; return JJ_ERR_INVALID; }
+    if (n > ((uint64_t)1 << 32) / strides[s]) { c->err = "jj_blake2b: more than 2^32 bytes of rows in one source"; return JJ_ERR_INVALID; }      // n * stride <= 2^32
+    rest += lens[s];
+  }
+  if (n == 0) return JJ_OK;
+  if (!out) return JJ_ERR_INVALID;
+  const size_t out_bytes = n * (size_t)digest_len;
+  if (((uintptr_t)out & 15u) && is_device_ptr(out)) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+  for (int s = 0; s < nsrc; s++) {
+    if (!srcs[s]) { c->err = "jj_blake2b: NULL source"; return JJ_ERR_INVALID; }
+    if (((uintptr_t)srcs[s] & 15u) && is_device_ptr(srcs[s])) { c->err = "device pointers must be 16-byte aligned"; return JJ_ERR_INVALID; }
+    const size_t in_bytes = (n - 1) * strides[s] + lens[s];
+    if ((uintptr_t)srcs[s] < (uintptr_t)out + out_bytes && (uintptr_t)out < (uintptr_t)srcs[s] + in_bytes) { c->err = "jj_blake2b: out overlaps a source"; return JJ_ERR_INVALID; }
+  }
+  int rc;
+  B2bSrcs S; memset(&S, 0, sizeof S);
+  for (int s = 0; s < nsrc; s++) {
+    const void* d;
+    if ((rc = stage_in(c, s, srcs[s], (n - 1) * strides[s] + lens[s], &d))) return rc;
+    S.p[s] = (const uint8_t*)d; S.stride[s] = (u64)strides[s];
+  }
+  OutRef o;
+  if ((rc = stage_out(c, c->out[0], out, out_bytes, &o))) return rc;
+  if (digest_len == 32) b2b_launch<32>(c, n, personal16, prefix, prefix_len, nsrc, lens, rest, S, o.dev);
+  else b2b_launch<64>(c, n, personal16, prefix, prefix_len, nsrc, lens, rest, S, o.dev);
+  bool sync = false;
+  if ((rc = finish_out(c, o, &sync))) return rc;
+  return finish(c, sync);
+}
 // ---- one RFC 8439 ChaCha20 key per row (kernel: k_chacha20_xor in jj_kernels.h; jj_chacha20.h): out[i][j] = in[i * in_stride + j] xor byte j of
 // the keystream of keys32[i] under nonce12, block counter from `counter`.  Every argument is checked before anything is staged or launched; ONE
 // launch over all n rows, no workspace.  A host `in` is staged as the (n - 1) * in_stride + len bytes that are read.  keys32 is read on the

@@ -2,8 +2,9 @@
 // code, everything in registers.  Unkeyed, 64-byte digest, zero salt, a 16-byte personalisation: parameter block word 0 = 0x01010040 xored into
 // h[0], the personalisation into h[6] and h[7]; t counts bytes in its low 64-bit word only (t1 = 0: inputs stay far below 2^64 bytes); f0 is set
 // on the last block, and the last block of an empty input is one zero block with t = 0.
-// Included by jj_kernels.h (k_sig_challenge, jj_sig_challenge; k_ka_kdf, jj_ka_kdf) and, with -DJJ_HOST_EMU, by tests/cpp/emu_blake2b.cpp and
-// tests/cpp/emu_ka.cpp.
+// Included by jj_kernels.h (k_sig_challenge, jj_sig_challenge; k_ka_kdf, jj_ka_kdf, jj_ka_kdf_each; k_blake2b, jj_blake2b: Blake2bRows at the
+// end of this file), by jj_abi.hip for that host midstate, and, with -DJJ_HOST_EMU, by tests/cpp/emu_blake2b.cpp, tests/cpp/emu_ka.cpp and
+// tests/cpp/emu_blake2b_rows.cpp.
 // The digest length is a compile-time parameter (Blake2bT<DIGEST>, 1..64 bytes; Blake2b = Blake2bT<64>): it enters the parameter word only --
 // BLAKE2b-256 is another hash than BLAKE2b-512 cut short -- and the first DIGEST bytes of h are the digest.  hash_parts is the one-compression
 // form jj_ka_kdf uses: one or two 32-byte parts and nothing else.
@@ -163,5 +164,110 @@ struct Blake2bT {
   }
 };
 typedef Blake2bT<64> Blake2b;
+
+// ---- rows gathered from several arrays (jj_blake2b, k_blake2b; with -DJJ_HOST_EMU tests/cpp/emu_blake2b_rows.cpp): the hashed string of row i
+// is  prefix || piece_0[i] || .. || piece_{np-1}[i].  The prefix is the same in every lane, so the host compresses its whole blocks once
+// (midstate: B = min(prefix_len / 128, (prefix_len + rest - 1) / 128) blocks, never a block that could be the final one) and the kernel gets
+// h, t0 = 128 B and the prefix's tail -- 0..128 bytes, zero-padded to 32 dwords -- as arguments: scalar registers.  A piece is `nd` dwords at
+// byte `off` of a row of source `src`; every length is a multiple of 4 and the same in every lane, so dword j of block b is EITHER a word of
+// the tail OR one aligned dword of one piece, the same piece in every lane: no funnel shift, no mask, and the block loop, the piece
+// boundaries and the final-block flag are uniform.  Every index into m[] is a compile-time constant (the 32 dwords of a block are an unrolled
+// loop; which piece serves dword j is a chain of uniform compares that selects one of four per-lane addresses): a run-time-indexed m[] would
+// go to scratch.  A dword that lies past the hashed string is not loaded at all.  Nothing in the instruction stream or in an address depends
+// on the data: the prefix may be a secret.
+constexpr int B2B_MAX_PIECES = 4;
+struct B2bMid { u64 h[8]; u64 t0; u32 tail[32]; u32 tail_len; };
+struct B2bPlan { u32 npieces; u32 src[B2B_MAX_PIECES], off[B2B_MAX_PIECES], nd[B2B_MAX_PIECES]; };     // unused pieces: nd = 0
+
+template <int DIGEST>
+struct Blake2bRows {
+  static_assert(DIGEST == 32 || DIGEST == 64, "jj_blake2b: digests of 32 or 64 bytes");
+  typedef Blake2bT<DIGEST> H;
+  static constexpr u32 BLOCK = 128;
+
+  // ---- the host's part: plain C++ (the device's compression is device code; this one never sees a final block)
+  static inline u64 le64(const uint8_t* p) { u64 x = 0; for (int i = 7; i >= 0; i--) x = (x << 8) | p[i]; return x; }
+  static inline u64 host_rotr(u64 x, int r) { return (x >> r) | (x << (64 - r)); }
+  static inline void host_compress(u64 (&h)[8], const u64 (&m)[16], u64 t) {
+    u64 v[16];
+    for (int i = 0; i < 8; i++) { v[i] = h[i]; v[8 + i] = H::IV[i]; }
+    v[12] ^= t;
+    static const uint8_t LANES[8][4] = {{0, 4, 8, 12}, {1, 5, 9, 13}, {2, 6, 10, 14}, {3, 7, 11, 15}, {0, 5, 10, 15}, {1, 6, 11, 12}, {2, 7, 8, 13}, {3, 4, 9, 14}};
+    for (int r = 0; r < 12; r++)
+      for (int q = 0; q < 8; q++) {
+        u64 &a = v[LANES[q][0]], &b = v[LANES[q][1]], &c = v[LANES[q][2]], &d = v[LANES[q][3]];
+        a = a + b + m[H::SIGMA[r % 10][2 * q]];     d = host_rotr(d ^ a, 32);
+        c = c + d;                                  b = host_rotr(b ^ c, 24);
+        a = a + b + m[H::SIGMA[r % 10][2 * q + 1]]; d = host_rotr(d ^ a, 16);
+        c = c + d;                                  b = host_rotr(b ^ c, 63);
+      }
+    for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
+  }
+  // Number of whole prefix blocks the host absorbs; `rest` = the bytes every row adds behind the prefix
+  static inline size_t midstate_blocks(size_t prefix_len, size_t rest) {
+    if (prefix_len + rest == 0) return 0;
+    const size_t a = prefix_len / BLOCK, b = (prefix_len + rest - 1) / BLOCK;
+    return a < b ? a : b;
+  }
+  // mid <- the state behind those blocks, t0, and the prefix's remaining bytes (0..128) zero-padded.  personal16 == nullptr: sixteen zero bytes.
+  static inline void midstate(B2bMid& mid, const uint8_t* personal16, const uint8_t* prefix, size_t prefix_len, size_t rest) {
+    const size_t blocks = midstate_blocks(prefix_len, rest);
+    for (int i = 0; i < 8; i++) mid.h[i] = H::IV[i];
+    mid.h[0] ^= H::PARAM0;
+    if (personal16) { mid.h[6] ^= le64(personal16); mid.h[7] ^= le64(personal16 + 8); }
+    u64 m[16];
+    for (size_t k = 0; k < blocks; k++) {
+      for (int j = 0; j < 16; j++) m[j] = le64(prefix + BLOCK * k + 8 * j);
+      host_compress(mid.h, m, (u64)BLOCK * (k + 1));
+    }
+    uint8_t pad[BLOCK] = {0};
+    for (size_t j = BLOCK * blocks; j < prefix_len; j++) pad[j - BLOCK * blocks] = prefix[j];
+    for (int j = 0; j < 32; j++) mid.tail[j] = (u32)pad[4 * j] | ((u32)pad[4 * j + 1] << 8) | ((u32)pad[4 * j + 2] << 16) | ((u32)pad[4 * j + 3] << 24);
+    mid.t0 = (u64)BLOCK * blocks; mid.tail_len = (u32)(prefix_len - BLOCK * blocks);
+  }
+  // one piece per source, in order: source s whole (lens[s] bytes from byte 0 of its rows)
+  static inline void plan_sources(B2bPlan& plan, int nsrc, const size_t* lens) {
+    plan.npieces = (u32)nsrc;
+    for (int k = 0; k < B2B_MAX_PIECES; k++) { plan.src[k] = k < nsrc ? (u32)k : 0u; plan.off[k] = 0; plan.nd[k] = k < nsrc ? (u32)(lens[k] / 4) : 0u; }
+  }
+
+  // ---- the lane's part
+  // the aligned dword at a 64-bit address of global memory (an address formed as an integer would otherwise be read with flat_load)
+  static JJ_DEV u32 load_dword(u64 addr) {
+#ifdef JJ_HOST_EMU
+    return *reinterpret_cast<const u32*>((uintptr_t)addr);
+#else
+    return *(const __attribute__((address_space(1))) u32*)addr;
+#endif
+  }
+  // out <- the digest finished from the midstate over  tail || piece_0 || .. || piece_3  as DIGEST / 4 little-endian words.  rowp[k] = the
+  // address of the first byte of piece k in THIS lane's row (unused where nd[k] = 0); everything else is the same in every lane.
+  static JJ_DEV void finish(u32 (&out)[DIGEST / 4], const B2bMid& mid, const B2bPlan& plan, const u64 (&rowp)[B2B_MAX_PIECES]) {
+    u64 h[8], m[16];
+    _Pragma("unroll") for (int i = 0; i < 8; i++) h[i] = mid.h[i];
+    const u32 c1 = plan.nd[0], c2 = c1 + plan.nd[1], c3 = c2 + plan.nd[2], total = c3 + plan.nd[3];      // stream dwords in front of pieces 1, 2, 3; all
+    // rowp[k] - 4 c_k: what 4 g is added to for a stream dword g of piece k (integers: the difference may lie in front of the array)
+    const u64 v0 = rowp[0], v1 = rowp[1] - 4ull * c1, v2 = rowp[2] - 4ull * c2, v3 = rowp[3] - 4ull * c3;
+    const u32 tail_dw = mid.tail_len / 4u;
+    const u32 bytes = mid.tail_len + 4u * total;                  // behind t0: at most 128 + 4 * 65536 bytes
+    const u32 nblocks = bytes ? (bytes + BLOCK - 1u) / BLOCK : 1u;
+    _Pragma("unroll 1") for (u32 blk = 0; blk < nblocks; blk++) {
+      u32 w[32];
+      _Pragma("unroll") for (int j = 0; j < 32; j++) {
+        w[j] = blk == 0 ? mid.tail[j] : 0u;
+        const u32 pos = 32u * blk + (u32)j;                       // dword of  tail || pieces
+        if (pos >= tail_dw && pos - tail_dw < total) {            // uniform
+          const u32 g = pos - tail_dw;
+          const u64 vb = g < c1 ? v0 : g < c2 ? v1 : g < c3 ? v2 : v3;
+          w[j] = load_dword(vb + 4ull * g);
+        }
+      }
+      _Pragma("unroll") for (int k = 0; k < 16; k++) m[k] = H::pair(w[2 * k], w[2 * k + 1]);
+      const bool last = blk + 1u == nblocks;
+      H::compress(h, m, mid.t0 + (last ? (u64)bytes : (u64)BLOCK * (blk + 1u)), last);
+    }
+    _Pragma("unroll") for (int i = 0; i < DIGEST / 8; i++) { out[2 * i] = (u32)h[i]; out[2 * i + 1] = (u32)(h[i] >> 32); }
+  }
+};
 
 }  // namespace jj

@@ -737,6 +737,27 @@ __global__ void __launch_bounds__(256, 3) k_varbase_mont_ka(size_t n, const u32*
   }
   ext.put(0, i, u); ext.put(1, i, v); ext.put(2, i, z);
 }
+// The same ladder with one secret scalar PER UNIT (jj_ka_kdf_each: the sender's esk_i against pk_d_i): the scalars are loaded like
+// k_varbase_mont's, with load8 per lane -- they are vector registers by nature, so nothing has to be hidden from the compiler --, the ladder
+// and the recovery are called as they are, and with COFACTOR the three doublings of k_varbase_mont_ka follow (the same bounds).
+// CONSTANT-TIME in the scalars and in the results; one unit per lane for every n (no quad-of-lanes form).
+template <bool COFACTOR>
+__global__ void __launch_bounds__(256, 3) k_varbase_mont_ka_each(size_t n, const void* scalars, const void* points, SoA ext) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 k[8];
+  load8(k, scalars, i);
+  Fe u, v, z, xq, zq, xp, zp;
+  const u32 last = varbase_mont_ladder(ext.get(2, i), k, xq, zq, xp, zp);
+  const Affine P = load_affine(points, i);
+  varbase_mont_recover(P, ext.get(2, i), last, xq, zq, xp, zp, u, v, z);
+  if constexpr (COFACTOR) {
+    Ext e; e.u = u; e.v = v; e.z = z; e.t1 = u; e.t2 = v;   // (Curve::dbl reads u, v, z only)
+    e = Curve::dbl(Curve::dbl(Curve::dbl(e)));
+    u = e.u; v = e.v; z = e.z;
+  }
+  ext.put(0, i, u); ext.put(1, i, v); ext.put(2, i, z);
+}
 #endif  // JJ_KERNELS_BATCH
 
 // ------------------------------------------------------------------------------------------------ K4: fixed-base
@@ -1213,6 +1234,37 @@ __global__ void __launch_bounds__(256) k_ka_kdf(size_t n, u64 personal_lo, u64 p
   Blake2bT<32>::hash_parts<INPUT ? 2 : 1>(w, personal_lo, personal_hi, a, b);
   if (!ok[i]) zero8(w);
   store8(key32, i, w);
+}
+#endif  // JJ_KERNELS_BATCH
+// Raw BLAKE2b digests over rows gathered from up to four arrays (jj_blake2b; Blake2bRows in jj_blake2b.h): out[i] = BLAKE2b-DIGEST(personal;
+// prefix || piece_0[i] || ..), one row per lane, ONE launch.  mid is the host's midstate over the prefix's whole blocks with t0 and the
+// prefix's tail; plan names for every piece its source, the byte offset in the source's row and its dwords; srcs the sources' bases and row
+// strides.  The byte offset of a row is formed in 64 bits (n * stride may reach 2^32); rows are read as aligned dwords (bases 4-byte aligned:
+// the entry point asks 16 of a device pointer; strides, offsets and lengths multiples of 4) and nothing is read outside a piece's own bytes.
+// Which source serves a piece is selected by compares on plan.src (uniform; no run-time-indexed array).  DIGEST bytes are written per lane as
+// 16-byte stores.  Nothing in the instruction stream or in an address depends on the data.
+struct B2bSrcs { const uint8_t* p[B2B_MAX_PIECES]; u64 stride[B2B_MAX_PIECES]; };
+#ifdef JJ_KERNELS_BATCH
+template <int DIGEST>
+__global__ void __launch_bounds__(256) k_blake2b(size_t n, B2bMid mid, B2bPlan plan, B2bSrcs srcs, void* out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u64 rowp[B2B_MAX_PIECES];
+  _Pragma("unroll") for (int k = 0; k < B2B_MAX_PIECES; k++) {
+    const u32 s = plan.src[k];
+    const uint8_t* base = s == 0 ? srcs.p[0] : s == 1 ? srcs.p[1] : s == 2 ? srcs.p[2] : srcs.p[3];
+    const u64 stride = s == 0 ? srcs.stride[0] : s == 1 ? srcs.stride[1] : s == 2 ? srcs.stride[2] : srcs.stride[3];
+    rowp[k] = (u64)(uintptr_t)base + (u64)i * stride + plan.off[k];
+  }
+  u32 d[DIGEST / 4];
+  Blake2bRows<DIGEST>::finish(d, mid, plan, rowp);
+  typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+  u32x4* p = reinterpret_cast<u32x4*>(static_cast<uint8_t*>(out) + i * (size_t)DIGEST);
+  _Pragma("unroll") for (int q = 0; q < DIGEST / 16; q++) {
+    u32x4 x = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
+    asm volatile("" : "+v"(x));                              // one four-register operand per store, as in k_blake2s
+    p[q] = x;
+  }
 }
 #endif  // JJ_KERNELS_BATCH
 // One RFC 8439 ChaCha20 key per row (jj_chacha20_xor, jj_chacha20.h): out[i][0 .. len) = in[i * in_stride .. + len) xor the keystream of

@@ -22,6 +22,7 @@ FLAG_PEDERSEN_POINT = 1        # jj_pedersen_hash_vartime only: 64 affine bytes 
 SIG_REJECT, SIG_OK, SIG_MALFORMED = 0, 1, 2      # verdict bytes of jj_sigverify_each
 REDJUBJUB_PERSONAL = b"Zcash_RedJubjubH"         # the personalisation of RedJubjub's challenge hash: the documented example of sig_challenge's `personal` (the C library does not contain it)
 SAPLING_KDF_PERSONAL = b"Zcash_SaplingKDF"       # the personalisation of the Sapling KDF: the documented example of ka_kdf's `personal` (the C library does not contain it)
+SAPLING_OCK_PERSONAL = b"Zcash_Derive_ock"       # the personalisation of Sapling's outgoing cipher key: the documented example of blake2b's `personal` in note_encrypt and ovk_open (the C library does not contain it)
 FLAG_KA_COFACTOR = 32          # jj_ka_kdf only: share = [8]([sk]P)
 FLAG_KA_HASH_INPUT = 64        # jj_ka_kdf only: hash share || encoding
 KA_SAPLING_FLAGS = FLAG_ZIP216 | FLAG_KA_COFACTOR | FLAG_KA_HASH_INPUT      # the Sapling recipient's ka_kdf flags
@@ -1427,6 +1428,167 @@ class Engine:
         both = ok & tag_ok
         plain *= both[:, None]
         return plain, both
+
+    # -------------------------------------------------------------- the sender's side of a note (jj_blake2b, jj_ka_kdf_each)
+    def blake2b(self, sources, personal=None, prefix=b"", digest_len=32, out=None):
+        """Raw BLAKE2b digests over rows gathered from several arrays (jj_blake2b) -> (n, digest_len):
+        out[i] = BLAKE2b-digest_len(personal; prefix || sources[0][i] || sources[1][i] || ..), digest_len 32 or 64 (BLAKE2b-256 is its own
+        hash, not a truncation).  sources: a list of up to four (n, L) uint8 arrays -- numpy arrays or CUDA tensors, mixed freely; L a multiple
+        of 4 in 4..65536 --; a strided view (buf[:, 16:48]) keeps its stride where that is a multiple of 4 and is read where it is, any other
+        layout is copied first.  One array may serve several sources.  personal: 16 bytes or None for sixteen zero bytes; prefix: up to 4096
+        bytes of HOST memory, a multiple of 4, the same for every row (it may be a viewing key: nothing in the instruction stream or in an
+        address depends on the data).  With no source every row is the digest of the prefix alone, and n is out's row count (1 without out).
+        The result is of the first source's kind, or `out`; a device result may be handed straight to aead_open or aead_seal as keys: they
+        read it on the same stream.  The library knows no protocol: SAPLING_OCK_PERSONAL with prefix = ovk and sources cv, cmu, epk is the
+        documented example."""
+        personal = _fixed_bytes(personal, 16, "personal")
+        prefix = bytes(prefix)
+        digest_len = int(digest_len)
+        if digest_len not in (32, 64):
+            raise ValueError("digest_len: 32 or 64 expected, got %d" % digest_len)
+        if len(prefix) > 4096 or len(prefix) % 4:
+            raise ValueError("prefix: at most 4096 bytes and a multiple of 4, got %d" % len(prefix))
+        sources = list(sources)
+        if len(sources) > 4:
+            raise ValueError("sources: at most four arrays")
+        srcs = []
+        for k, s in enumerate(sources):
+            r = _Rows(s, "sources[%d]" % k)
+            if r.n > 1 and r.stride % 4:                  # a row stride the kernel cannot read as dwords: a contiguous copy
+                r = _Rows(r.keep.contiguous() if r.torch else np.ascontiguousarray(r.keep), "sources[%d]" % k)
+            if r.len < 4 or r.len > 65536 or r.len % 4:
+                raise ValueError("sources[%d]: rows of a multiple of 4 in 4..65536 bytes expected, got %d" % (k, r.len))
+            srcs.append(r)
+        if srcs:
+            n = srcs[0].n
+        elif out is not None:
+            n = _Arg(out, digest_len).n
+        else:
+            n = 1
+        if any(s.n != n for s in srcs):
+            raise ValueError("length mismatch: %d rows expected in every source" % n)
+        if n > 1 << 24 or any(n * s.stride > 1 << 32 for s in srcs):
+            raise ValueError("at most 2^24 rows and 2^32 bytes of rows per source and call")
+        oa = None
+        if out is None and srcs:
+            out, optr = self._alloc(srcs[0], n, digest_len)
+        elif out is None:
+            out = np.empty((n, digest_len), np.uint8)
+            optr = out.ctypes.data
+        else:
+            oa = _Arg(out, digest_len)
+            if oa.n != n or oa.keep is not out:
+                raise ValueError("out: a contiguous uint8 array of %d x %d bytes expected" % (n, digest_len))
+            optr = oa.ptr
+        self._bind_stream(srcs + ([oa] if oa is not None else []))
+        cs = (C.c_void_p * 4)(*[s.ptr for s in srcs])
+        cl = (C.c_size_t * 4)(*[s.len for s in srcs])
+        cst = (C.c_size_t * 4)(*[max(s.stride, s.len) for s in srcs])
+        self._check(self._lib.jj_blake2b(self._ctx, C.c_size_t(n), C.c_int(digest_len), personal, prefix or None, C.c_size_t(len(prefix)), C.c_int(len(srcs)),
+                                         cs, cl, cst, optr))
+        return out
+
+    def ka_kdf_each(self, sk, P, personal=None, flags=KA_SAPLING_FLAGS, hash_input=None, out=None):
+        """Key agreement with one secret scalar PER ROW and its KDF (jj_ka_kdf_each) -> (keys (n, 32), ok (n,)): exactly ka_kdf, but sk is
+        (n, 32) -- each row read as varbase_mul reads a scalar: the low 252 bits, an integer never reduced mod r -- and, with
+        FLAG_KA_HASH_INPUT, the second hashed part is hash_input[i] when hash_input (n, 32) is given and P[i] when it is None (the sender
+        hashes share || epk, and epk is not the point that was multiplied).  hash_input without that flag is refused.  sk, P, hash_input:
+        numpy arrays or CUDA tensors, mixed freely; the results are of P's kind, or `out` = (keys, ok).  CONSTANT-TIME in the scalars and the
+        shares; the points are public."""
+        personal = _fixed_bytes(personal, 16, "personal")
+        if not hasattr(P, "shape") or len(P.shape) != 2 or P.shape[1] != 32:
+            raise ValueError("P: shape (n, 32) expected, got %r" % (tuple(P.shape) if hasattr(P, "shape") else None,))
+        n = P.shape[0]
+        ska, pa = _Arg(sk, 32), _Arg(P, 32)
+        ha = None if hash_input is None else _Arg(hash_input, 32)
+        if ska.n != n or (ha is not None and ha.n != n):
+            raise ValueError("sk and hash_input: %d rows of 32 bytes expected, one per row of P" % n)
+        if ha is not None and not flags & FLAG_KA_HASH_INPUT:
+            raise ValueError("hash_input needs FLAG_KA_HASH_INPUT")
+        if out is None:
+            (keys, kptr), (ok, okptr) = self._alloc(pa, n, 32), self._alloc(pa, n, 1)
+        else:
+            keys, ok = out
+            ka, oa = _Arg(keys, 32), _Arg(ok, 1)
+            if ka.n != n or oa.n != n or ka.torch != pa.torch or oa.torch != pa.torch or ka.keep is not keys or oa.keep is not ok:
+                raise ValueError("out: (keys, ok), contiguous uint8 arrays of %d x 32 and %d bytes of P's kind expected" % (n, n))
+            kptr, okptr = ka.ptr, oa.ptr
+        self._bind_stream([pa, ska] + ([ha] if ha is not None else []))
+        self._check(self._lib.jj_ka_kdf_each(self._ctx, C.c_size_t(n), ska.ptr, pa.ptr, ha.ptr if ha is not None else None, C.c_uint(flags), personal, kptr, okptr))
+        return keys, ok
+
+    def _same_kind(self, like, arrays):
+        """`arrays` as (n, w) arrays of `like`'s kind (numpy, or CUDA tensors on its device)"""
+        if _is_torch(like):
+            import torch
+
+            return [x if _is_torch(x) else torch.from_numpy(_host_bytes(x).reshape(tuple(x.shape))).to(like.device) for x in arrays]
+        return [x.cpu().numpy() if _is_torch(x) else _host_bytes(x).reshape(tuple(np.shape(x))) for x in arrays]
+
+    def note_encrypt(self, esk, gd, pkd, plain, ovk32, cv, cmu, kdf_personal, ock_personal, flags=KA_SAPLING_FLAGS):
+        """The ciphertexts of n outputs -> (epk (n, 32), c_enc (n, L + 16), c_out (n, 80)), of plain's kind.  esk (n, 32): one fresh secret
+        scalar per output; gd (n, 64): the diversified bases as affine points; pkd, cv, cmu (n, 32); plain (n, L), L a multiple of 4 in
+        4..1024; ovk32: 32 bytes of host memory.  Steps, all on plain's device (with CUDA tensors neither a key nor a share visits the host):
+        epk = varbase_mul_compressed(esk, gd), the CONSTANT-TIME ladder; keys = ka_kdf_each(esk, pkd, kdf_personal, flags, hash_input=epk);
+        c_enc = aead_seal(keys, plain); ock = blake2b([cv, cmu, epk], ock_personal, prefix=ovk32); c_out = aead_seal(ock, pkd || esk) --
+        zero nonce, empty aad.  SAPLING_KDF_PERSONAL and SAPLING_OCK_PERSONAL are the documented examples; the library knows no protocol.
+        A pkd that the decoder refuses gives that row the all-zero note key (ka_kdf_each's rule): check pkd where it is not the caller's own."""
+        ovk32 = _fixed_bytes(bytes(_host_bytes(ovk32)), 32, "ovk32")
+        esk, gd, pkd, cv, cmu = self._same_kind(plain, [esk, gd, pkd, cv, cmu])
+        epk = self.varbase_mul_compressed(esk, gd)
+        keys, _ = self.ka_kdf_each(esk, pkd, kdf_personal, flags, hash_input=epk)
+        c_enc = self.aead_seal(keys, plain)
+        ock = self.blake2b([cv, cmu, epk], ock_personal, prefix=ovk32)
+        if _is_torch(plain):
+            import torch
+
+            op = torch.cat([pkd, esk], dim=1)
+        else:
+            op = np.concatenate([pkd, esk], axis=1)
+        return epk, c_enc, self.aead_seal(ock, op)
+
+    def ovk_open(self, ovk32, cv, cmu, epk, c_out, c_enc, kdf_personal, ock_personal, flags=KA_SAPLING_FLAGS):
+        """Recover sent notes with an outgoing viewing key -> (plain (n, L), op (n, 64), ok (n,)), of c_enc's kind.  cv, cmu, epk (n, 32);
+        c_out (n, 80); c_enc (n, L + 16).  First stage, over all n rows -- one BLAKE2b block and one 80-byte AEAD open per output, no scalar
+        multiplication: ock = blake2b([cv, cmu, epk], ock_personal, prefix=ovk32); op = pk_d || esk from aead_open(ock, c_out).  Second
+        stage, over the rows that HIT only: esk canonical (fr from_bytes' ok), ka_kdf_each(esk, pk_d, kdf_personal, flags, hash_input=epk),
+        aead_open of c_enc.  The hit rows are gathered with index operations of numpy or torch: the ONE place where this call
+        waits for the device (the number of hits sizes the second stage).  The results are scattered back into full-size zero arrays: ok is the AND of
+        the four verdicts, and every row that is not ok is zeros in plain and in op.  CONSTANT-TIME in esk and the shares like
+        ka_kdf_each; which rows hit is the public outcome of the scan."""
+        ovk32 = _fixed_bytes(bytes(_host_bytes(ovk32)), 32, "ovk32")
+        shape = tuple(c_enc.shape) if hasattr(c_enc, "shape") else None
+        if shape is None or len(shape) != 2 or shape[1] < 20:
+            raise ValueError("c_enc: shape (n, L + 16) expected, got %r" % (shape,))
+        n, L = shape[0], shape[1] - 16
+        cv, cmu, epk, c_out = self._same_kind(c_enc, [cv, cmu, epk, c_out])
+        ock = self.blake2b([cv, cmu, epk], ock_personal, prefix=ovk32)
+        op, hit = self.aead_open(ock, c_out)
+        if _is_torch(c_enc):
+            import torch
+
+            idx = torch.nonzero(hit).reshape(-1)                         # waits for the device
+            plain = torch.zeros((n, L), dtype=torch.uint8, device=c_enc.device)
+            op_out, ok = torch.zeros_like(op), torch.zeros_like(hit)
+        else:
+            idx = np.nonzero(hit)[0]
+            plain, op_out, ok = np.zeros((n, L), np.uint8), np.zeros_like(op), np.zeros_like(hit)
+        if len(idx) == 0:
+            return plain, op_out, ok
+        op_h = op[idx]
+        pkd, esk = op_h[:, :32], op_h[:, 32:]
+        if _is_torch(c_enc):
+            pkd, esk = pkd.contiguous(), esk.contiguous()
+        else:
+            pkd, esk = np.ascontiguousarray(pkd), np.ascontiguousarray(esk)
+        _, fr_ok = self.field_unary_ok("fr", "from_bytes", esk)
+        keys, ka_ok = self.ka_kdf_each(esk, pkd, kdf_personal, flags, hash_input=epk[idx])
+        plain_h, tag_ok = self.aead_open(keys, c_enc[idx])
+        good = fr_ok.reshape(-1) & ka_ok & tag_ok
+        plain[idx] = plain_h * good[:, None]
+        op_out[idx] = op_h * good[:, None]
+        ok[idx] = good
+        return plain, op_out, ok
 
     def _b2s_args(self, msgs, personal, prefix):
         personal = _fixed_bytes(personal, 8, "personal")

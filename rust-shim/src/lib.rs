@@ -273,6 +273,29 @@ impl Gpu {
         assert_eq!(unsafe { jj_ka_kdf(self.0, n, sk.as_ptr() as _, p.as_ptr() as _, flags, personal.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), keys.as_mut_ptr() as _, ok.as_mut_ptr()) }, 0);
         (keys, ok)
     }
+    /// The same with one secret scalar PER ROW (`jj_ka_kdf_each`: the sender's side of a note): `sk[i]` is read as `jj_varbase_mul` reads a
+    /// scalar; with flag 64 the second hashed part is `hash_input[i]` when `hash_input` is given and `p[i]` when it is `None`.  Constant-time in
+    /// the scalars and in the shares.
+    pub fn ka_kdf_each(&self, sk: &[[u8; 32]], p: &[[u8; 32]], hash_input: Option<&[[u8; 32]]>, flags: u32, personal: Option<&[u8; 16]>) -> (Vec<[u8; 32]>, Vec<u8>) {
+        let n = p.len();
+        assert!(sk.len() == n && hash_input.map_or(true, |h| h.len() == n));
+        let mut keys = vec![[0u8; 32]; n];
+        let mut ok = vec![0u8; n];
+        assert_eq!(unsafe { jj_ka_kdf_each(self.0, n, sk.as_ptr() as _, p.as_ptr() as _, hash_input.map_or(std::ptr::null(), |h| h.as_ptr() as *const c_void), flags, personal.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), keys.as_mut_ptr() as _, ok.as_mut_ptr()) }, 0);
+        (keys, ok)
+    }
+    /// Raw BLAKE2b digests over rows gathered from up to four arrays (`jj_blake2b`): `out[i] = BLAKE2b-digest_len(personal; prefix || S_0[i] || ..)`,
+    /// `S_s[i]` the `lens[s]` bytes at byte `i * strides[s]` of `sources[s]`; `digest_len` 32 or 64; lengths, strides and the prefix's length
+    /// multiples of 4.  Returns `n x digest_len` bytes, dense.  `personal`: `None` is sixteen zero bytes.  The library knows no protocol
+    /// (Sapling's ock: `digest_len` 32, `prefix` = ovk, the sources cv, cmu, epk).
+    pub fn blake2b(&self, n: usize, digest_len: c_int, personal: Option<&[u8; 16]>, prefix: &[u8], sources: &[&[u8]], lens: &[usize], strides: &[usize]) -> Vec<u8> {
+        assert!(sources.len() == lens.len() && sources.len() == strides.len() && sources.len() <= 4 && (digest_len == 32 || digest_len == 64));
+        assert!(n == 0 || sources.iter().zip(lens.iter().zip(strides)).all(|(s, (l, st))| st >= l && s.len() >= (n - 1) * st + l));
+        let ptrs: Vec<*const c_void> = sources.iter().map(|s| s.as_ptr() as *const c_void).collect();
+        let mut out = vec![0u8; n * digest_len as usize];
+        assert_eq!(unsafe { jj_blake2b(self.0, n, digest_len, personal.map_or(std::ptr::null(), |x| x.as_ptr() as *const c_void), if prefix.is_empty() { std::ptr::null() } else { prefix.as_ptr() as _ }, prefix.len(), sources.len() as c_int, ptrs.as_ptr(), lens.as_ptr(), strides.as_ptr(), out.as_mut_ptr() as _) }, 0);
+        out
+    }
     /// One RFC 8439 ChaCha20 key per row (`jj_chacha20_xor`): rows of `len` bytes at a stride of `in_stride` in `input`, a dense `n x len` result;
     /// `len` and `in_stride` multiples of 4, `len` in 4..=1024; `nonce`: `None` is twelve zero bytes.
     pub fn chacha20_xor(&self, keys: &[[u8; 32]], nonce: Option<&[u8; 12]>, counter: u32, input: &[u8], len: usize, in_stride: usize) -> Vec<u8> {

@@ -18,6 +18,8 @@ tests/kernel_reach.json and tests/kernel_reach_ledger.json are the ledgers of ea
   python tools/kernel_reach.py DIR                                                   both in turn
   python tools/kernel_reach.py --add DIR                                             no GPU: a new GPU test file that adds no kernel -- the files
       traced into DIR (--trace DIR --files test_gpu_new.py) enter the committed ledger, every other file's entries and the header stay
+  python tools/kernel_reach.py --add DIR --add-kernels                               no GPU: the same for a change whose new kernels only its new
+      test files launch -- the compiled kernels the ledger lacks enter it first (the library's assembly is compiled, ~2 minutes)
   python tools/kernel_reach.py --check                                               no GPU: the committed ledger as a table
 """
 import argparse
@@ -238,11 +240,21 @@ def build_ledger(outdir, asm=None):
     return kernels
 
 
-def add_to_ledger(outdir):
+def add_to_ledger(outdir, new_kernels=False):
     """--add: the per-file results in outdir replace those files' entries in the committed ledger; every other file's counts, and the header of
-    the full trace, stay.  For a change that adds a GPU test file and no kernel: the compiled names must be the ledger's."""
+    the full trace, stay.  For a change that adds GPU test files and, with new_kernels (--add-kernels), the kernels only they launch: a
+    compiled kernel the ledger lacks enters it without a launch, and the traced files are then expected to give it one.  A name the ledger
+    holds and the library no longer compiles is an error either way: that takes a trace of every file."""
     ledger = json.load(open(LEDGER))
     kernels = ledger["kernels"]
+    if new_kernels:
+        compiled = set(compiled_kernels())
+        gone = sorted(set(kernels) - compiled)
+        if gone:
+            raise SystemExit("in the ledger but no longer compiled: %s: trace every file again" % ", ".join(gone))
+        for name in sorted(compiled - set(kernels)):
+            kernels[name] = {"files": {}, "largest": None, "smallest": None}
+            print("new kernel: %s" % name)
     for path in sorted(glob.glob(os.path.join(outdir, "test_gpu_*.json"))):
         rec = json.load(open(path))
         if rec["untraced_rc"] or rec["traced_rc"]:
@@ -306,6 +318,7 @@ def main():
     ap.add_argument("--trace", metavar="DIR")
     ap.add_argument("--ledger", metavar="DIR")
     ap.add_argument("--add", metavar="DIR", help="no GPU: put the files traced into DIR (--trace DIR --files ...) into the committed ledger, the other files' entries kept")
+    ap.add_argument("--add-kernels", action="store_true", help="with --add: kernels the library compiles and the ledger lacks enter it (compiles the assembly, ~2 minutes)")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--files", default="", help="comma-separated subset of the GPU test files (a long suite is traced over several calls into one DIR)")
     ap.add_argument("--untraced-limit", type=int, default=600, help="seconds allowed to a file's untraced run")
@@ -313,7 +326,7 @@ def main():
     if a.check:
         return check()
     if a.add:
-        add_to_ledger(a.add)
+        add_to_ledger(a.add, a.add_kernels)
         return 0
     files = [f for f in a.files.split(",") if f] or gpu_files()
     assert all(f in gpu_files() for f in files), files
